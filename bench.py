@@ -15,18 +15,28 @@ max-over-ranks wall time of the timed steps (inputs resident in HBM).
 
 The timed data does not depend on --warmup: every run first develops the
 cavity for --develop (400) untimed steps from rest (97 % of p' non-zero, vs 3 %
-after 20), then runs the W warm-up steps, then times K steps.  After timing, one
-more step runs on the GPU and on the CPU oracle from the same developed state
-and the two are compared bit for bit (`parity_developed_step`).
+after 20), then runs the W warm-up steps, then times K steps.
+
+A plain run stops there: it prints the result line (headline, configuration
+and the roofline figures of the timed steps themselves) and, with
+`--dump-outputs DIR`, writes the state the last timed step left as
+DIR/<name>.npy (the same arguments give the same inputs, so two builds can be
+compared output for output).  `--full` adds every leg that takes runs of its
+own.  After timing, one more step runs on the GPU and on the CPU oracle from
+the same developed state and the two are compared bit for bit
+(`parity_developed_step`); then the per-phase times, the second-order leg, the
+reference-control-flow legs (C2, C3), the 8192^2 control, the reference's
+default grid and the CPU baselines (N > 1: per-rank phases and the sharded
+parity step).
 
 roofline: `achieved` is the one-pass HBM bytes of a Jacobi launch (read p',
 read rhs, write p' once: 12 B x slab cells) over the measured
 launch time; a launch performs T sweeps on chip, so `algorithmic_sweep_equiv`
-reports the 12 B x cells x T figure separately.  At N=1 a second entry,
-`roofline_control`, times the same kernel family on 8192^2 (T = 8), whose
-768 MB Jacobi working set cannot live in the 256 MB Infinity Cache.
+reports the 12 B x cells x T figure separately.  With `--full` at N=1 a second
+entry, `roofline_control`, times the same kernel family on 8192^2 (T = 8),
+whose 768 MB Jacobi working set cannot live in the 256 MB Infinity Cache.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 `--gpus N` with N > 1 and no external launcher (WORLD_SIZE unset): this
@@ -328,6 +338,33 @@ SCALAR_KEYS = ("dt", "simulation_time", "simulation_step", "last_p_residual", "l
                "last_v_residual", "jacobi_sweeps_total")
 
 
+DUMP_SEED = 20240607
+DUMP_MAX_BYTES = 56 << 20      # all field files of all ranks together (f32), below 64 MB
+
+
+def dump_outputs(path, state, rank, world):
+    """--dump-outputs: what the timed path left after its last timed step, as
+    a caller of Model::update reads it back (get_state): the seven fields as
+    f32 and the scalars as one f64 vector in SCALAR_KEYS order.  A field
+    larger than its share of DUMP_MAX_BYTES is sampled at positions drawn
+    from a generator seeded by (DUMP_SEED, field index, field size) alone, so
+    two builds run with the same arguments write the same positions.  N > 1:
+    every rank writes its slab as <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (4 * len(STATE_KEYS) * max(world, 1))
+    sfx = f".rank{rank}" if world > 1 else ""
+    for i, k in enumerate(STATE_KEYS):
+        a = np.ascontiguousarray(state[k], dtype=np.float32).ravel()
+        if a.size > cap:
+            idx = np.random.default_rng([DUMP_SEED, i, a.size]).integers(0, a.size, cap)
+            idx.sort()
+            a = a[idx]
+        np.save(os.path.join(path, f"{k}{sfx}.npy"), a)
+    np.save(os.path.join(path, f"scalars{sfx}.npy"),
+            np.array([float(state[k]) for k in SCALAR_KEYS], dtype=np.float64))
+
+
 def parity_sharded_step(model, dist, rank, world, grid, params, device):
     """N > 1: one more step on the slabs, checked against the same step of a
     single-domain GPU model of the whole grid started from the gathered slab
@@ -595,6 +632,15 @@ def main():
                     help="skip the reference's default_grid() channel leg at N=1")
     ap.add_argument("--launch-timeout", type=float, default=1800.0,
                     help="seconds the self-launched ranks of --gpus N may take")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg: the bitwise "
+                         "parity step against the oracle, per-phase times, the second-order, "
+                         "reference-control-flow, 8192^2 control and default-grid legs and the "
+                         "CPU baselines (N > 1: per-rank phases and the sharded parity step); "
+                         "the --no-* options trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left (u, v, p, u_star, v_star, "
+                         "p_prime, rhs and the scalars) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher and rank plumbing only (gloo, no GPU, no HIP library): "
                          "prints a line with dry_run true and no measurement")
@@ -698,6 +744,8 @@ def main():
             raise
         res = None
     state = model.get_state()   # this rank's slab
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, rank, world)
     finite = bool(np.isfinite(state["u"]).all() and np.isfinite(state["v"]).all())
     nonzero = float(np.count_nonzero(state["p_prime"])) / max(state["p_prime"].size, 1)
     subn = int(((np.abs(state["p_prime"]) > 0) &
@@ -713,7 +761,7 @@ def main():
     roof_valu = roofline_valu(kname, f"{nx}x{model.nyl}", launch_ms, nblk)
     geometry = model.jacobi_geometry(persist=nblk > 1)
     multi = {}
-    if n > 1:
+    if n > 1 and args.full:
         # collective legs, after the timed steps (every rank takes part):
         # per-rank phase and RCCL exchange times, then the sharded parity step
         ph = phase_window(model, 5)
@@ -781,14 +829,14 @@ def main():
             "final_step": int(state["simulation_step"]), "final_dt": float(state["dt"]),
             "fields_finite": finite and res is not None,
         }
-        if n > 1:
+        if n > 1 and args.full:
             out["rank_phases"] = multi["rank_phases"]
             ps = multi.get("parity_sharded_step")
             if ps is not None:
                 out["parity_sharded_step"] = ps["ok"]
                 out["parity_sharded_step_detail"] = ps.get("detail", "") + (
                     "" if ps["ok"] else f"; differ: {ps['differ']}")
-        if n == 1 and not args.no_parity and out["fields_finite"]:
+        if n == 1 and args.full and not args.no_parity and out["fields_finite"]:
             ok, bad = parity_developed_step(model, nx, ny, args.iters, args.re, state,
                                             cpu_threads())
             out["parity_developed_step"] = ok
@@ -796,19 +844,19 @@ def main():
                 f"1 step from step {state['simulation_step']} on GPU and oracle "
                 f"(oracle/cfd_oracle.c), every word of u, v, p, u*, v*, p', rhs and the "
                 f"scalars compared" + ("" if ok else f"; differ: {bad}"))
-        if n == 1:
+        if n == 1 and args.full:
             out["phases"] = phase_window(model, 5)
-        if n == 1 and not args.no_so:
+        if n == 1 and args.full and not args.no_so:
             out["so_step"] = so_leg(args, cfdamd, local, nx, ny)
-        if n == 1 and not args.no_parity_mode:
+        if n == 1 and args.full and not args.no_parity_mode:
             out["parity_mode"] = {
                 "C2": parity_mode_leg(args, cfdamd, local, 1024, 400.0, 100),
                 "C3": parity_mode_leg(args, cfdamd, local, 4096, 1000.0, 200)}
-        if n == 1 and not args.no_control:
+        if n == 1 and args.full and not args.no_control:
             out["roofline_control"] = control_run(args, cfdamd, local)
-        if n == 1 and not args.no_reference_default:
+        if n == 1 and args.full and not args.no_reference_default:
             out["reference_default"] = reference_default_leg(args, cfdamd, local)
-        if n == 1 and not args.no_cpu_baseline:
+        if n == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nx, ny, args.iters, args.re, args.cpu_budget, state)
             nt = cpu_threads()
             if nt > 1:

@@ -82,7 +82,7 @@ def test_bench_self_launch_two_ranks_loopback():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CFD_BENCH_LOOPBACK="1", CFD_RCCL_TIMEOUT_S="60")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
                         "--steps", "3", "--warmup", "1", "--develop", "10", "--nx", "1024",
                         "--ny", "512", "--iters", "64"], env=env, capture_output=True,
                        text=True, timeout=300)

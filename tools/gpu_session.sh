@@ -27,7 +27,7 @@ P="--develop 30 --warmup 0 --steps 2"
 has suite && step suite 900 env PYTHONUNBUFFERED=1 python -u -m pytest tests -x -v -m gpu --timeout 400 --timeout-method thread
 has tests && step tests 900 python -u -m pytest ${TESTS} -x -v -m gpu --timeout 400 --timeout-method thread
 has smoke && step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-has bench && step bench_default 600 python3 bench.py
+has bench && step bench_default 600 python3 bench.py --full
 if has stats; then
   step stats_bench 300 rocprofv3 --kernel-trace --stats -d $D -o bench --output-format csv -- $B --steps 20 --warmup 5
   step stats_control 300 rocprofv3 --kernel-trace --stats -d $D -o control --output-format csv -- $B --nx 8192 --ny 8192 --steps 10
