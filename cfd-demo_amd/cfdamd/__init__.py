@@ -458,6 +458,14 @@ class Model:
         return int(n.value)
 
     @property
+    def sums_launches(self) -> int:
+        """Per-launch Jacobi marches run in the guarded fma form
+        (cfd_get_sums_launches)."""
+        n = C.c_uint64()
+        check("cfd_get_sums_launches", load().cfd_get_sums_launches(self._hh(), C.byref(n)))
+        return int(n.value)
+
+    @property
     def comm_calls(self) -> int:
         """Halo-exchange groups + all-reduces enqueued (cfd_get_comm_calls)."""
         n = C.c_uint64()

@@ -34,6 +34,16 @@ __device__ __forceinline__ void publish_max(uint32_t *set, int key, float m) {
     if (m > 0.0f) atomicMax(&set[(key & (kResSlots - 1)) * kResStride], __float_as_uint(m));
 }
 
+// |x| as bits: NaN and Inf compare above every finite value as unsigned integers
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+// Raise a bound word (Ctl::sums_m0 / sums_rm) to this lane's maximum of
+// abs_bits where it exceeds the threshold the launch publishes anyway: no
+// lane does on a sane field, so this is one compare and an untaken branch --
+// no reduction, no load, no atomic at the wave's tail.
+__device__ __forceinline__ void raise_bits_bound(uint32_t *word, uint32_t m, uint32_t thr) {
+    if (m > thr) atomicMax(word, m);
+}
+
 // NaN or +-Inf (the step's failure check, SURVEY.md §5: the reference itself
 // has none and keeps stepping on a blown-up field).
 __device__ __forceinline__ bool nonfinite(float x) { return !(fabsf(x) <= 3.40282347e38f); }
@@ -175,6 +185,10 @@ __device__ __forceinline__ void solve_finalize_body(const Geom &g, const Fields 
         if (pass >= 0 && pass + 1 <= kMaxPasses)
             c->go[pass + 1] = (go && !(check_break && g.tol_enabled && c->last_p < g.p_tol)) ? 1 : 0;
         if (exact_flips >= 2) c->spec_stop = c->spec_redo = c->spec_launch = c->spec_launches = 0;
+        // the fma form's maxima described the p' this solve started from:
+        // only the next corrector finish makes them valid again (Ctl::sums_state)
+        c->sums_state = 0u;
+        c->sums_m0 = 0u;
         go_s = go;
     }
     __syncthreads();

@@ -24,6 +24,10 @@
 namespace cfd {
 
 constexpr int kGhostUV = 2;
+// thresholds of the fma form's bounds (Ctl::sums_m0 / sums_rm): R max|p'| <=
+// 2^122 and 0.1875 kMaxSweeps max|rhs| <= 768 * 2^112 < 2^122 keep the guard's
+// sum below its 2^123
+constexpr float kSumsPLim = 0x1p122f, kSumsRLim = 0x1p112f;
 constexpr int kMaxSweeps = 4096;   // per pressure solve
 constexpr int kMaxPasses = 64;     // corrector passes + 1
 
@@ -76,7 +80,19 @@ struct Ctl {
     uint32_t nonfinite_step;   // sticky: simulation_step after the first step whose
                                // velocities were not all finite (0 = never)
     uint32_t vis[2];        // render: max key, max ~key of the derived field (cfd_render.hip)
-    uint32_t done;          // (unused since r6: the last-workgroup folds were removed; keeps the layout)
+    // The fma form of the per-launch march (LdsMarch SUMS == 2) and its
+    // whole-solve guard.  sums_m0 / sums_rm are upper bounds of max |p'| /
+    // max |rhs| (bits & 0x7fffffff): the publishing kernel raises the word to
+    // a fixed threshold (kSumsPLim / R, kSumsRLim: together they pass the
+    // guard) and only a lane that holds a larger value raises it further, so
+    // the usual launch issues ONE atomic.  sums_state: 0 the bounds describe
+    // nothing a solve may rely on; 1 the corrector finish bounded the p' the
+    // next step's solve starts from in sums_m0 and zeroed sums_rm; 2 the
+    // predictor march then bounded the rhs it formed in sums_rm.  Only
+    // a solve that finds 2 may take the form; every k_finalize_solve (and the
+    // resident solve's own) returns to 0 and zeroes sums_m0, and every host
+    // call that can change p' or rhs outside a step returns to 0.
+    uint32_t sums_state;
     uint64_t sweeps_total;
     // speculative temporal blocking with the tolerance on (k_spec_check):
     // spec_stop: a launch of this solve converged (later launches skip);
@@ -84,7 +100,8 @@ struct Ctl {
     // (0: none, it converged on its last stage); spec_launches: launches run
     // (the finalize's buffer flips).  All 0 between solves.
     int32_t spec_stop, spec_redo, spec_launch, spec_launches;
-    uint32_t spec_done;     // (unused since r6; keeps the layout)
+    uint32_t sums_launches; // per-launch marches that ran the fma form (diagnostics)
+    uint32_t sums_m0, sums_rm;   // max |p'| / max |rhs| as bits & 0x7fffffff (NaN, Inf: above every finite)
     int32_t go[kMaxPasses + 1];      // go[p]: pass p of the corrector loop runs
     uint32_t err[kMaxSweeps];        // per-sweep max |p'new - p'| as f32 bits
 };
@@ -146,6 +163,12 @@ struct Fields {
     // the RCCL watchdog's evidence of forward progress
     uint32_t *host_progress;
     uint32_t *persist;   // kPersistWords words after the slot sets (see kPersistFlagStride)
+    // the fma form of the per-launch march can run for this model at all (one
+    // domain, Jacobi with a fixed count, a grid that allows the form, knob
+    // on): only then do the corrector finish and the predictor march keep
+    // Ctl::sums_state and its bounds; 0: they skip that bookkeeping entirely,
+    // sums_state stays 0 and every launch runs the reference's body
+    int32_t sums_track;
 };
 
 // ---- launchers (cfd_kernels.hip) ----

@@ -126,9 +126,16 @@ constexpr int ring_depth(int T, int PD, int G) {
 // that bound per task before it picks SUMS (its guard); otherwise, and for
 // every other launch, the reference's form runs.
 // (r5's optimistic per-wave SUMS form for per-launch solves and r4's
-// whole-solve guard lost their A/B against the reference's form and were
-// removed in r6: every per-launch march runs the reference's form.)
-template <int T, int FAST, int MODE, bool SUMS = false>
+// whole-solve guard, measured inside the march, lost their A/B against the
+// reference's form and were removed in r6.)
+// SUMS == 2 (r7, per-launch fixed-count solves of one domain): the fma form,
+// fma(h + v, 1/dx^2, -rhs) -- both multiplies and the subtraction in one
+// instruction, 9 VALU instead of 11.  Bitwise the same under the same bound
+// ((h + v) * R is exact, so the fma rounds once, where the reference's
+// subtraction does).  k_jacobi_lds picks it per launch from the whole-solve
+// guard whose maxima the corrector finish and the predictor march publish
+// (Ctl::sums_state), and runs it as a second complete march.
+template <int T, int FAST, int MODE, int SUMS = 0>
 struct LdsMarch {
     static constexpr bool RES = MODE == 1 || MODE == 5, SPEC = MODE == 2, REDO = MODE == 3;
     // MODE 4 (PERSIST): a block of k_jacobi_persist; p' moves between
@@ -230,7 +237,14 @@ struct LdsMarch {
         const f2 h = {hx, hy};
         const f2 v = Tp + B;
         f2 s;
-        if constexpr (SUMS) {
+        if constexpr (SUMS == 2) {
+            // (h + v) * R - Rh in one fma: (h + v) * R is exact (a scaling by
+            // a power of two below overflow) and equals the reference's hz +
+            // vt, so the fma's single rounding is the reference's subtraction
+            const f2 d = __builtin_elementwise_fma(h + v, (f2){r_dx_sq, r_dx_sq}, -Rh);
+            const f2 pu = d * r_denom;
+            return 0.75f * pu + 0.25f * C;
+        } else if constexpr (SUMS == 1) {
             s = (h + v) * r_dx_sq;   // == h * r_dx_sq + v * r_dy_sq under the guard
         } else {
             const f2 hz = fdiv2<FAST>(h, dx_sq, r_dx_sq);
@@ -448,7 +462,7 @@ struct LdsMarch {
 // trk (persistent blocks): per wave, trk[3 w .. 3 w + 2] = max |p'| of the
 // rows it stored, of the p' rows it loaded and of the rhs rows it used (the
 // last two only in the reference's form; 0 where not tracked or no rows).
-template <int T, int FAST, int MODE, bool SUMS = false>
+template <int T, int FAST, int MODE, int SUMS = 0>
 __device__ __forceinline__ void lds_block(const Geom &g, float *__restrict__ pa,
                                           float *__restrict__ pb, const float *__restrict__ rhs,
                                           Ctl *ctl, uint32_t *res_slots, int par, int out_lo,
@@ -629,7 +643,7 @@ template <int T, int FAST, int MODE>
 __global__ __launch_bounds__(kLdsWaves * 64, lds_min_waves(MODE)) void k_jacobi_lds(
     Geom g, float *__restrict__ pa, float *__restrict__ pb, const float *__restrict__ rhs,
     Ctl *ctl, uint32_t *res_slots, int pass, int par, int out_lo, int out_hi, int nwc, int nseg,
-    int wlo, int whi, int it, int lag) {
+    int wlo, int whi, int it, int lag, float sums_c) {
     using M = LdsMarch<T, FAST, MODE>;
     [[maybe_unused]] constexpr bool RES = M::RES;   // the stamp guard's
     __shared__ f2 lds[kLdsWaves * M::D * 64];
@@ -687,6 +701,27 @@ __global__ __launch_bounds__(kLdsWaves * 64, lds_min_waves(MODE)) void k_jacobi_
             par = ctl->spec_launch;   // re-run that launch: same source, same destination
         }
         if (nst <= 0) return;
+    }
+    // The fma form (LdsMarch SUMS == 2), fixed-count launches of one domain:
+    // sums_c = 0.1875 * kMaxSweeps (the most sweeps any solve has: the bound
+    // holds for every launch of every solve, whatever its count) where the
+    // grid allows the form (launch_lds_t), else 0.  A sweep moves max |p'| by at most 0.1875 Rm / R
+    // (Rm = max |rhs|, R = 1/dx^2) and the boundary copies never raise it, so
+    // every |p'| of the solve stays below M0 + sums_c Rm / R; the form runs
+    // when that is below 2^123 / R (then R |h|, R |v| < 2^127).  M0 and Rm
+    // are the finish's and the predictor march's maxima (Ctl::sums_state);
+    // NaN / Inf bits make the sum NaN or Inf and fail the test.  One branch,
+    // wave-uniform, between two complete marches that share only arguments.
+    if constexpr (FAST == 1 && MODE <= 1) {
+        if (sums_c > 0.0f && ctl->sums_state == 2u) {
+            const float bound = __uint_as_float(ctl->sums_m0) * g.r_dx_sq + sums_c * __uint_as_float(ctl->sums_rm);
+            if (bound < 0x1p123f) {
+                if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&ctl->sums_launches, 1u);
+                lds_block<T, FAST, MODE, 2>(g, pa, pb, rhs, ctl, res_slots, par, out_lo, out_hi, nwc, nseg,
+                                            wlo, whi, lds, nst, xcd_block(g));
+                return;
+            }
+        }
     }
     lds_block<T, FAST, MODE>(g, pa, pb, rhs, ctl, res_slots, par, out_lo, out_hi, nwc, nseg, wlo,
                              whi, lds, nst, xcd_block(g));
@@ -1082,6 +1117,19 @@ int lds_segments(const Geom &g, int nrows, int nwc, int pad, int occ_override = 
     return std::max(1, std::min(per_round * rounds, nrows / kMinRows));
 }
 
+// The grid allows the scaled-sum forms (LdsMarch SUMS): reciprocal multiply,
+// dx^2 == dy^2 with a power-of-two reciprocal R >= 1 (h * R, v * R exact
+// below overflow); CFD_JACOBI_SUMS=0 keeps the reference's form everywhere.
+// Read per launch (one getenv) so tests can change it.
+inline bool lds_sums_grid(const Geom &g) {
+    const char *ue = getenv("CFD_JACOBI_SUMS");
+    int exp2 = 0;
+    const float R = g.r_dx_sq;
+    const bool pow2 = R >= 1.0f && std::frexp(R, &exp2) == 0.5f;
+    return !(ue && atoi(ue) == 0) && g.fastdiv == 1 && g.dx_sq == g.dy_sq && g.r_dx_sq == g.r_dy_sq &&
+           pow2;
+}
+
 template <int T, int MODE>
 void launch_lds_t(const Geom &g, const Fields &f, int pass, int par, int it, int out_lo, int out_hi,
                   uint32_t *rs, hipStream_t s, int lag = 0) {
@@ -1101,9 +1149,14 @@ void launch_lds_t(const Geom &g, const Fields &f, int pass, int par, int it, int
     const int reach = T + 2;
     const int wlo = out_lo - reach <= 1 - g.j0 ? kEdgeWeight : 16;
     const int whi = out_hi + reach >= g.ny - 2 - g.j0 ? kEdgeWeight : 16;
-#define CFD_LDS_LAUNCH(FASTV)                                                                      \
+    // the fma form's guard constant (k_jacobi_lds): fixed-count launches of
+    // one domain (a slab's bound would need its neighbours' maxima) on a grid
+    // that allows the form; the sweeps of a solve are at most kMaxSweeps
+    const float sums_c =
+        MODE <= 1 && g.j0 == 0 && g.nyl == g.ny && lds_sums_grid(g) ? 0.1875f * kMaxSweeps : 0.0f;
+#define CFD_LDS_LAUNCH(FASTV)                                                                     \
     hipLaunchKernelGGL((k_jacobi_lds<T, FASTV, MODE>), grid, block, pad, s, g, pa, pb, f.rhs, f.ctl, \
-                       rs, pass, par, out_lo, out_hi, nwc, nseg, wlo, whi, it, lag)
+                       rs, pass, par, out_lo, out_hi, nwc, nseg, wlo, whi, it, lag, sums_c)
     if (g.fastdiv == 1)
         CFD_LDS_LAUNCH(1);
     else if (g.fastdiv == 2)
@@ -1207,12 +1260,8 @@ bool launch_lds_persist_t(const Geom &g, const Fields &f, int pass, int par0, in
     // the SUMS form (LdsMarch): reciprocal multiply, dx^2 == dy^2 with a
     // power-of-two reciprocal R >= 1 (h * R, v * R exact below overflow);
     // CFD_JACOBI_SUMS=0 keeps the reference's form everywhere
-    const char *ue = getenv("CFD_JACOBI_SUMS");
-    int exp2 = 0;
     const float R = g.r_dx_sq;
-    const bool pow2 = R >= 1.0f && std::frexp(R, &exp2) == 0.5f;
-    const int sums = !(ue && atoi(ue) == 0) && g.fastdiv == 1 && g.dx_sq == g.dy_sq &&
-                     g.r_dx_sq == g.r_dy_sq && pow2;
+    const int sums = lds_sums_grid(g);
     const float plim = sums ? std::ldexp(1.0f, 124) / R : 0.0f, rlim = std::ldexp(1.0f, 124);
 #define CFD_LDS_PLAUNCH(FASTV)                                                                     \
     hipLaunchKernelGGL((k_jacobi_persist<T, FASTV>), grid, block, pad, s, g, pa, pb, f.rhs, f.ctl, \

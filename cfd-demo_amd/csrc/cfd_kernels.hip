@@ -1312,6 +1312,7 @@ __global__ __launch_bounds__(kBlock) void k_correct_finish4m(Geom g, Fields f, f
     Ctl *c = f.ctl;
     const int nx = g.nx;
     float du = 0.f, dv = 0.f, mu = 0.f, mv = 0.f;
+    uint32_t pm = 0u;
     bool bad = false;
     const int bid = xcd_block(g);
     const int i0 = 4 * ((bid % nbx) * kBlock + (int)threadIdx.x);
@@ -1332,10 +1333,26 @@ __global__ __launch_bounds__(kBlock) void k_correct_finish4m(Geom g, Fields f, f
             if (lj < g.nyl || vrow) pc = *reinterpret_cast<const float4 *>(pp + (long)lj * nx + i0);
             cf4_row<SP>(g, f, pp, inlet, dt, i0, lj, pc, vrow ? pb : make_float4(0.f, 0.f, 0.f, 0.f),
                         du, dv, mu, mv, bad);
+            if (f.sums_track && lj < g.nyl)
+                pm = max(max(pm, max(abs_bits(pc.x), abs_bits(pc.y))), max(abs_bits(pc.z), abs_bits(pc.w)));
             pb = pc;
         }
     }
     flag_nonfinite(c, bad);
+    // a bound of max |p'| over the owned rows, the p' the next step's solve
+    // starts from (warm start), for its fma-form guard (Ctl::sums_state; the
+    // word is zero since the solve's finalize): the threshold, raised by any
+    // lane that read more (NaN and Inf included).  The next predictor march
+    // bounds the rhs in sums_rm.
+    if (f.sums_track) {
+        const uint32_t thr = __float_as_uint(kSumsPLim * g.dx_sq);   // 2^122 / R, exact
+        raise_bits_bound(&c->sums_m0, pm, thr);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            atomicMax(&c->sums_m0, thr);
+            c->sums_rm = 0u;
+            c->sums_state = 1u;
+        }
+    }
     __shared__ float red[kBlock / 64][4];
     du = wave_max(du);
     dv = wave_max(dv);

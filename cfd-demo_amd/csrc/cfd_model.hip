@@ -1960,6 +1960,13 @@ struct cfd_model {
         ck_open = false;
         ck_replay.clear();
     }
+    // The fma form's maxima (Ctl::sums_state) describe the p' and rhs of
+    // "finish of step n-1, then predictor march of step n": every entry point
+    // that can change either outside that sequence drops them first.
+    int invalidate_sums() {
+        HIP_TRY(hipMemsetAsync(&ctl->sums_state, 0, 4, stream));
+        return 0;
+    }
     // the abort word and the resident solve's barrier lines (its counters,
     // generations and exit ticket stay where an aborted launch left them)
     int clear_abort_words() {
@@ -2095,6 +2102,24 @@ void apply_params(cfd_model *m, const cfd_params *p) {
     m->g.tol_enabled = p->tol_enabled ? 1 : 0;
     m->g.p_tol = p->p_tol;
     m->g.jacobi_iters = p->jacobi_iters;
+}
+
+// Fields::sums_track: whether the fma form of the per-launch march can ever
+// run for this model -- one domain, the Jacobi solver with a fixed count, the
+// grid test of lds_sums_grid (cfd_jacobi_lds.h: reciprocal multiply, dx^2 ==
+// dy^2 with a power-of-two reciprocal >= 1) and the CFD_JACOBI_SUMS knob as
+// it stands now.  Kernel arguments of a captured step freeze it, which is
+// safe: with 0 the publishers never set Ctl::sums_state and every launch runs
+// the reference's body; with 1 the launch still reads the knob itself.
+// Called when the model is created and after every parameter change.
+void set_sums_track(cfd_model *m) {
+    const Geom &g = m->g;
+    const char *ue = getenv("CFD_JACOBI_SUMS");
+    int e2 = 0;
+    const bool pow2 = g.r_dx_sq >= 1.0f && std::frexp(g.r_dx_sq, &e2) == 0.5f;
+    m->f.sums_track = !(ue && atoi(ue) == 0) && m->n_ranks == 1 && g.j0 == 0 && g.nyl == g.ny &&
+                      m->params.pressure_solver == CFD_SOLVER_JACOBI && !g.tol_enabled &&
+                      g.fastdiv == 1 && g.dx_sq == g.dy_sq && g.r_dx_sq == g.r_dy_sq && pow2;
 }
 
 // Pick the cheapest division form that is bit-identical to IEEE `/` for ALL
@@ -2391,6 +2416,8 @@ int build_model(cfd_model *m, const cfd_grid *grid, const cfd_params *p, int dev
     f.vis_slots = f.red_slots + (size_t)4 * kResSlots * kResStride;
     f.persist = m->slots + (size_t)(kMaxSweeps + 16) * kResSlots * kResStride;
 
+    set_sums_track(m);
+
     Ctl c0;
     std::memset(&c0, 0, sizeof(c0));
     c0.dt = p->dt;
@@ -2679,6 +2706,7 @@ int cfd_update_n(cfd_model *m, int n) {
 int cfd_piso_step(cfd_model *m, float dt_sub) {
     if (!m) return fail(CFD_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->invalidate_sums()) return rc;
     if (int rc = m->ck_begin()) return rc;
     auto run = [m, dt_sub]() {
         int rc = m->exchange_uv();
@@ -2693,6 +2721,7 @@ int cfd_pressure_solve(cfd_model *m, float *residual_out) {
     if (!m) return fail(CFD_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
     int rc;
+    if ((rc = m->invalidate_sums())) return rc;
     if (m->host_driven()) {
         return m->enqueue_solve_host_driven(residual_out);
     }
@@ -2714,6 +2743,7 @@ int cfd_pressure_solve(cfd_model *m, float *residual_out) {
 int cfd_run_phase(cfd_model *m, int phase, float dt_sub) {
     if (!m) return fail(CFD_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->invalidate_sums()) return rc;
     switch (phase) {
     case CFD_PHASE_U_PREDICTOR: {
         int rc = m->exchange_uv();
@@ -2754,6 +2784,9 @@ int cfd_set_params(cfd_model *m, const cfd_params *p) {
         m->host_cur = c.cur;
     }
     apply_params(m, p);
+    set_sums_track(m);
+    rc = m->invalidate_sums();
+    if (rc) return rc;
     // set_parameters overwrites dt (model.rs:1252)
     HIP_TRY(hipMemcpy(&m->ctl->dt, &p->dt, 4, hipMemcpyHostToDevice));
     return 0;
@@ -2902,6 +2935,8 @@ int cfd_set_state(cfd_model *m, const cfd_state *st) {
     c.nonfinite_step = 0;   // a new state: failure detection starts over
     c.red[4] = 0;
     c.red[6] = 0;           // and an old solve timeout with it
+    c.sums_state = 0;       // a new p' / rhs: the fma form's maxima describe the old ones
+    c.sums_m0 = 0;
     rc = m->clear_abort_words();
     if (rc) return rc;
     HIP_TRY(hipMemcpy(m->f.ctl, &c, offsetof(Ctl, go), hipMemcpyHostToDevice));
@@ -2931,6 +2966,9 @@ int cfd_profile_sweeps(cfd_model *m, int n_sweeps, double *avg_ms_out) {
     if (!m) return fail(CFD_EINVAL, "null model");
     if (n_sweeps < 1 || n_sweeps > kMaxSweeps) return fail(CFD_EINVAL, "n_sweeps out of range");
     HIP_TRY(hipSetDevice(m->device));
+    // sweeps p' outside a step, like the other entry points that drop the fma
+    // form's bounds (its finalize below resets them as well)
+    if (int rc = m->invalidate_sums()) return rc;
     const int lo = std::max(0, 1 - (int)m->j0), hi = std::min(m->g.nyl, (int)m->g.ny - 1 - (int)m->j0);
     hipEvent_t a = m->ev_prof0, b = m->ev_prof1;
     Geom g = m->g;
@@ -3097,6 +3135,15 @@ int cfd_get_persist_sums(cfd_model *m, uint64_t *blocks) {
     uint32_t v = 0;
     HIP_TRY(hipMemcpy(&v, m->f.persist + 3, 4, hipMemcpyDeviceToHost));
     *blocks = v;   // persistent blocks run in the SUMS form
+    return 0;
+}
+
+int cfd_get_sums_launches(cfd_model *m, uint64_t *launches) {
+    if (!m || !launches) return fail(CFD_EINVAL, "null argument");
+    Ctl c;
+    int rc = m->read_ctl(&c);
+    if (rc) return rc;
+    *launches = c.sums_launches;   // per-launch marches run in the fma form
     return 0;
 }
 

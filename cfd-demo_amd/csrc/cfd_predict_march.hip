@@ -73,6 +73,7 @@ struct PredMarch {
     // value is needed at once would wait for every row load in flight
     float UB[D], VB[D];
     float vs[4];      // v*(k), carried from the previous step
+    uint32_t rmax;    // max |rhs| bits of the rows this lane stored (Ctl::sums_rm)
     const Geom *g;
     Fields f;
     __amdgpu_buffer_rsrc_t rs_u, rs_v, rs_us, rs_vs;
@@ -203,6 +204,9 @@ struct PredMarch {
                     rh.z = (sdiv<SP>(us[3] - us[2], dx, rdx) + sdiv<SP>(vn[2] - vs[2], dy, rdy)) / dt;
                     rh.w = (sdiv<SP>(east - us[3], dx, rdx) + sdiv<SP>(vn[3] - vs[3], dy, rdy)) / dt;
                     *reinterpret_cast<float4 *>(f.rhs + (long)k * nx + i0) = rh;
+                    if (f.sums_track)
+                        rmax = max(max(rmax, max(abs_bits(rh.x), abs_bits(rh.y))),
+                                   max(abs_bits(rh.z), abs_bits(rh.w)));
                 } else if (c == nch && upred) {
                     f.u_star[ku] = us[0];   // face nx
                 }
@@ -253,6 +257,14 @@ __global__ __launch_bounds__(kBlock, CFD_PM_WPE) void k_predict_march(Geom g, Fi
         c->inlet = st < 100u ? ((float)st / 100.0f) * g.target_inlet : g.target_inlet;
         c->go[0] = 1;
     }
+    // the fma form's rhs bound (Ctl::sums_state): a launch over all owned
+    // rows after the corrector finish (which zeroed the word) publishes the
+    // threshold; a lane that stores a larger |rhs| raises it (below)
+    if (f.sums_track && blockIdx.x == 0 && threadIdx.x == 0 && row_lo == 0 && row_hi == g.nyl &&
+        f.ctl->sums_state == 1u) {
+        atomicMax(&f.ctl->sums_rm, __float_as_uint(kSumsRLim));
+        f.ctl->sums_state = 2u;
+    }
     PredMarch<SCHEME, SP, MASK, R> m;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lane = (int)threadIdx.x & 63;
@@ -286,6 +298,7 @@ __global__ __launch_bounds__(kBlock, CFD_PM_WPE) void k_predict_march(Geom g, Fi
     m.dt = dt_of(f.ctl, dt_override);
 #pragma unroll
     for (int q = 0; q < 4; ++q) m.vs[q] = 0.0f;
+    m.rmax = 0u;
     // interior wave: every chunk it touches has columns in [3, nx-3] (so the
     // last chunk nch is not among them), and the steady steps' faces (u row
     // k, v row k+1, k = r0+1 .. r1-2) lie on global rows [2, ny-3] / [2, ny-2]
@@ -297,6 +310,7 @@ __global__ __launch_bounds__(kBlock, CFD_PM_WPE) void k_predict_march(Geom g, Fi
         m.template run<true>();
     else
         m.template run<false>();
+    if (f.sums_track) raise_bits_bound(&f.ctl->sums_rm, m.rmax, __float_as_uint(kSumsRLim));
 }
 
 }  // namespace

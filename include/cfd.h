@@ -267,6 +267,12 @@ int cfd_get_persist_steals(cfd_model *m, uint64_t *steals);
  * (k_jacobi_persist's per-task guard), summed over the model's life.
  * Synchronises.  (new; diagnostics) */
 int cfd_get_persist_sums(cfd_model *m, uint64_t *blocks);
+/* Per-launch marches (k_jacobi_lds, fixed-count solves of one domain) that ran
+ * the fma form -- fma(h + v, 1/dx^2, -rhs), two instructions per column pair
+ * and sweep fewer -- under the whole-solve guard whose maxima the corrector
+ * finish and the predictor march publish, summed over the model's life.
+ * CFD_JACOBI_SUMS=0 keeps it at 0.  Synchronises.  (new; diagnostics) */
+int cfd_get_sums_launches(cfd_model *m, uint64_t *launches);
 /* Collective calls this (sharded) model has enqueued: halo-exchange groups
  * and all-reduces, summed over its life (0 unsharded).  (new; diagnostics) */
 int cfd_get_comm_calls(const cfd_model *m, uint64_t *n);
