@@ -1,5 +1,5 @@
 // cfd_device.h — device helpers shared by the kernel translation units
-// (cfd_kernels.hip, cfd_jacobi_tb1.hip, cfd_jacobi_pipe*.hip).  Everything is
+// (cfd_kernels.hip, cfd_jacobi_tb1.hip, cfd_jacobi_pipe.hip, ...).  Everything is
 // internal to each translation unit (anonymous namespace).
 #pragma once
 #include "cfd_internal.h"

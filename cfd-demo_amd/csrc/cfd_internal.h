@@ -127,17 +127,16 @@ struct Geom {
     int32_t tb_rows;      // fixed output rows per wave segment (0: balanced by tb_bpc)
     int32_t tb_bpc;       // target k_jacobi_tb blocks per CU (balanced segmentation)
     int32_t n_cu;         // compute units of the device
-    int32_t tb_kind;      // 1: k_jacobi_tb (T <= 4); prefetch pipeline (T <= 8) with
-                          // 3: 4 columns per lane, 4: 2 columns per lane; 5: the
-                          // 2-column march with its rhs window in LDS
+    int32_t tb_kind;      // 1: k_jacobi_tb (T <= 4); 4: the prefetch pipeline (T <= 8,
+                          // 2 columns per lane, k_jacobi_pipe); 5: the same march
+                          // with its rhs window in LDS (k_jacobi_lds)
     int32_t xcd_remap;    // renumber blocks so each XCD gets contiguous tiles (xcd_block)
     // reciprocals of dx, dy, dx*dx, dy*dy; sp_pow2 = 1 when all four spacings
     // are exact powers of two (then sdiv multiplies, bit-identically)
     float r_dx, r_dy, r_dxx, r_dyy;
     int32_t sp_pow2;
     int32_t pred_div;     // predictors + divergence: 2: one row march (k_predict_march, both
-                          // schemes), 1: fused 2-row tile (k_predict_div, first order),
-                          // 0: separate launches; where the fused forms apply
+                          // schemes) where it applies, 0: separate launches
     int32_t res_div;      // r4: the resident solve's division mode: fastdiv, or 3 (FMA-corrected
                           // above 2^-96, IEEE below; proven like the others) where fastdiv is 0
 };
@@ -182,10 +181,6 @@ void launch_u_predictor(const Geom &g, const Fields &f, float dt_override, hipSt
 void launch_v_predictor(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
 // u and v predictors in one pass (same results as the two launches above).
 void launch_predict(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
-// first-order predictors + divergence in one row march (k_predict_div), when
-// predict_div_fused(): replaces launch_predict + the step's first divergence
-bool predict_div_fused(const Geom &g, const Fields &f);
-void launch_predict_div(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
 // both schemes' predictors + divergence in one row march (cfd_predict_march.hip),
 // when predict_march_ok(): replaces launch_predict + the step's first divergence
 bool predict_march_ok(const Geom &g, const Fields &f);
@@ -223,16 +218,14 @@ bool launch_jacobi_persist(const Geom &g, const Fields &f, int pass, int par0, i
 // (cfd_jacobi_lds8.hip).
 void lds_geometry8(const Geom &g, int out_lo, int out_hi, bool persist, int *pad, int *occ, int *nwc,
                    int *nseg);
-// The block kernels behind it: k_jacobi_tb (T <= 4, cfd_jacobi_tb1.hip) and
-// the prefetch-pipelined march with 4 or 2 columns per lane (T <= 8,
-// cfd_jacobi_pipe4.hip / cfd_jacobi_pipe2.hip).
+// The block kernels behind it: k_jacobi_tb (kind 1, T <= 4, cfd_jacobi_tb1.hip)
+// and the prefetch-pipelined march, 2 columns per lane (kind 4, T <= 8,
+// cfd_jacobi_pipe.hip).
 // res_slots: the slot set the last sweep's residual goes to, or null.
 void launch_tb1(const Geom &g, const Fields &f, int T, int pass, int it, int par, int out_lo,
                 int out_hi, uint32_t *res_slots, hipStream_t s);
-void launch_pipe4(const Geom &g, const Fields &f, int T, int pass, int it, int par, int out_lo,
-                  int out_hi, uint32_t *res_slots, hipStream_t s);
-void launch_pipe2(const Geom &g, const Fields &f, int T, int pass, int it, int par, int out_lo,
-                  int out_hi, uint32_t *res_slots, hipStream_t s);
+void launch_pipe(const Geom &g, const Fields &f, int T, int pass, int it, int par, int out_lo,
+                 int out_hi, uint32_t *res_slots, hipStream_t s);
 // kind 5: the same march with its rhs window in LDS (cfd_jacobi_lds.hip, T <= 8);
 // mode 2 / 3: the speculative launch / its re-run (launch_jacobi_spec)
 bool launch_lds_persist8(const Geom &g, const Fields &f, int pass, int par0, int nblk, int out_lo,
@@ -376,8 +369,7 @@ void launch_abort_from_red(const Fields &f, hipStream_t s);
 
 // Jacobi kernel geometry (exported for the roofline bookkeeping in bench).
 constexpr int kJacRowsPerWave = 16;
-constexpr int kMaxTemporal = 8;     // sweeps per temporally blocked launch (kind 3; 4 otherwise)
-constexpr int kTbRowsPerWave = 32;  // output rows per wave segment (TB kernel)
+constexpr int kMaxTemporal = 8;     // most sweeps per temporally blocked launch (kind 1: 4)
 constexpr int kJacWavesPerBlock = 4;
 
 }  // namespace cfd

@@ -1659,7 +1659,6 @@ struct cfd_model {
     int enqueue_piso(float dt_override, bool finish = false) {
         // K1-K3: the fused march when it applies, else predictors + divergence
         const bool march = predict_march_ok(g, f);
-        const bool fused = march || predict_div_fused(g, f);
         phase_mark(0, false);
         if (march && finish && uv_async) {
             // rows [2, nyl-2) read u rows >= 0 and <= nyl-1 and v rows <= nyl;
@@ -1671,12 +1670,10 @@ struct cfd_model {
             launch_predict_march(g, f, dt_override, stream, false, g.nyl - 4, g.nyl);
         } else if (march)
             launch_predict_march(g, f, dt_override, stream, finish && step_begin_folded);
-        else if (fused)
-            launch_predict_div(g, f, dt_override, stream);
         else
             launch_predict(g, f, dt_override, stream);
         auto first_divergence = [&](int pass) {
-            if (!fused) launch_divergence(g, f, pass, dt_override, stream);
+            if (!march) launch_divergence(g, f, pass, dt_override, stream);
             phase_mark(0, true);
         };
         if (finish) {
@@ -2234,9 +2231,6 @@ int build_model(cfd_model *m, const cfd_grid *grid, const cfd_params *p, int dev
         int rc0 = choose_division(m->stream, g);
         if (rc0) return rc0;
     }
-    // kind 4 (prefetch-pipelined march, 2 columns per lane) at T = 4 is the
-    // fastest measured geometry on the bench workload (tools/tune_tb.py, r1:
-    // 8.45 us/sweep vs 11.05 for kind 1 and 11.3 for kind 3 at its best T)
     // Default Jacobi march (measured at 4096^2 on developed fields, r2:
     // profiles/r2/tune_r2b_kind5.log, ab_lds_*.log): with the proven-exact
     // reciprocal multiply, kind 5 (rhs window in LDS, DPP-folded sums) at
@@ -2247,17 +2241,18 @@ int build_model(cfd_model *m, const cfd_grid *grid, const cfd_params *p, int dev
     // 7.3e11 vs 6.1e11 cell-updates/s at T = 8).  Single domain and slabs alike.
     g.tb_kind = g.fastdiv == 1 ? 5 : 4;
     g.pred_div = 2;
-    if (const char *e = getenv("CFD_PRED_DIV")) g.pred_div = std::min(std::max(atoi(e), 0), 2);
+    if (const char *e = getenv("CFD_PRED_DIV")) g.pred_div = atoi(e) == 0 ? 0 : 2;
     if (const char *kv = getenv("CFD_TB_KIND")) {
         const int k = atoi(kv);
-        g.tb_kind = (k == 3 || k == 4 || k == 5) ? k : 1;
+        if (k != 1 && k != 4 && k != 5) return fail(CFD_EINVAL, "CFD_TB_KIND must be 1, 4 or 5");
+        g.tb_kind = k;
     }
-    // the pipelined kernels (kinds 3/4) park masked lanes at a far voffset
-    // that must not wrap past 2^32 when the row offset is added: slabs up to
-    // 1 GiB per field (kind 5 bases its descriptors at each wave's rows)
+    // kind 4 parks masked lanes at a far voffset that must not wrap past 2^32
+    // when the row offset is added: slabs up to 1 GiB per field (kind 5 bases
+    // its descriptors at each wave's rows)
     if (g.tb_kind != 5 && (uint64_t)(g.nyl + 2 * g.hg) * (uint64_t)nx * 4u > (1ull << 30))
         g.tb_kind = 1;
-    m->t_max = g.tb_kind == 3 ? 6 : 4;
+    m->t_max = 4;
     {
         // kind 4 past the 256 MB Infinity Cache: 8 sweeps per launch halve the
         // HBM traffic (8192^2: 2.33e12 vs 1.38e12 cell-updates/s, r1)
@@ -3093,7 +3088,7 @@ int cfd_get_jacobi_kernel(const cfd_model *m, int *kind, char *name, size_t name
         else if (k == 5)
             snprintf(buf, sizeof buf, "k_jacobi_lds<%d, %d, 0>", T, m->g.fastdiv);
         else
-            snprintf(buf, sizeof buf, "k_jacobi_pipe<%d, %d, %d>", T, m->g.fastdiv, k == 3 ? 4 : 2);
+            snprintf(buf, sizeof buf, "k_jacobi_pipe<%d, %d>", T, m->g.fastdiv);
         snprintf(name, name_len, "%s", buf);
     }
     return 0;

@@ -243,8 +243,8 @@ int cfd_get_halo_depth(const cfd_model *m);
  * and sweeps per launch (1 when the tolerance is on). */
 int cfd_get_kernel_config(const cfd_model *m, int *fastdiv, int *temporal);
 /* The Jacobi kernel a solve launches: kind 0 single sweep (k_jacobi), 1
- * register-march temporal blocking (k_jacobi_tb), 3 / 4 the
- * prefetch-pipelined march with 4 / 2 columns per lane (k_jacobi_pipe), 5 the
+ * register-march temporal blocking (k_jacobi_tb), 4 the prefetch-pipelined
+ * register march, 2 columns per lane (k_jacobi_pipe), 5 the
  * LDS row march (k_jacobi_lds; with the tolerance on its speculative form), 6
  * the tolerance-mode solve of a small grid as one resident launch
  * (k_jacobi_resident, default up to 2^21 cells; CFD_RESIDENT=0/1 forces), and

@@ -156,9 +156,9 @@ def test_fused_finish_channel(scheme, profile, tol):
 @pytest.mark.parametrize("case", ["cavity", "channel_fo", "channel_passes", "wide_ragged",
                                   "cavity_so", "channel_so", "wide_ragged_so", "tall_so"])
 def test_predict_div_fused_matches_unfused(monkeypatch, case):
-    """The fused predictor + divergence kernels vs the separate predictor and
-    k_divergence launches, every field bitwise: k_predict_march (CFD_PRED_DIV=2,
-    both schemes) and k_predict_div (=1, first order).  Covers segment edges
+    """The fused predictor + divergence march vs the separate predictor and
+    k_divergence launches (CFD_PRED_DIV=0), every field bitwise: k_predict_march
+    (CFD_PRED_DIV=2, both schemes).  Covers segment edges
     (ny not a multiple of the segment), wave columns of 62 / 63 chunks (nx/4 + 1
     not a multiple), face 0 / face nx / column 0, the flat wrap reads of the
     last chunk, obstacle masks, corrector passes (later divergences unfused)."""
@@ -181,7 +181,7 @@ def test_predict_div_fused_matches_unfused(monkeypatch, case):
                     c.SimulationParams(corrector_passes=0, jacobi_iters=15, velocity_scheme=so), 5),
     }
     grid, params, steps = cases[case]
-    modes = ("0", "2") if params.velocity_scheme == so else ("0", "1", "2")
+    modes = ("0", "2")
     out = {}
     for fused in modes:
         monkeypatch.setenv("CFD_PRED_DIV", fused)
@@ -305,9 +305,8 @@ def test_control_handle_run_loop():
 
 @pytest.mark.parametrize("fastdiv,temporal,kind", [
     ("0", "1", "1"), ("0", "4", "1"), ("1", "1", "1"), ("1", "3", "1"), ("1", "4", "1"),
-    ("1", "8", "3"), ("0", "8", "3"), ("1", "5", "3"), ("1", "6", "3"), ("1", "7", "3"),
-    ("1", "4", "3"), ("1", "3", "3"), ("1", "2", "3"), ("1", "1", "3"), ("2", "8", "3"),
-    ("2", "4", "1"), ("1", "6", "4"), ("1", "8", "4"), ("0", "8", "4"), ("1", "4", "4"),
+    ("2", "4", "1"), ("0", "1", "4"), ("0", "4", "4"), ("2", "4", "4"),
+    ("1", "6", "4"), ("1", "8", "4"), ("0", "8", "4"), ("1", "4", "4"),
     ("1", "7", "4"), ("1", "5", "4"), ("1", "3", "4"), ("1", "2", "4"), ("1", "1", "4"),
     ("2", "6", "4"),
     ("1", "8", "5"), ("1", "7", "5"), ("1", "6", "5"), ("1", "5", "5"), ("1", "4", "5"),
@@ -315,9 +314,10 @@ def test_control_handle_run_loop():
     ("0", "4", "5"), ("2", "5", "5")])
 def test_kernel_variants_bitwise(monkeypatch, fastdiv, temporal, kind):
     """Every Jacobi kernel variant (IEEE or proven-exact fast division; 1..8
-    sweeps per launch; kinds 1, 3, 4 and 5) gives the oracle's bits, on a power-of-two cavity (where
-    the reciprocal multiply is exact) and on the reference's default channel
-    grid (non-power-of-two divisors)."""
+    sweeps per launch; kinds 1, 4 and 5, and at one sweep per launch kind 0,
+    the single-sweep k_jacobi) gives the oracle's bits, on a power-of-two
+    cavity (where the reciprocal multiply is exact) and on the reference's
+    default channel grid (non-power-of-two divisors)."""
     c = _cfd()
     monkeypatch.setenv("CFD_FASTDIV", fastdiv)
     monkeypatch.setenv("CFD_TEMPORAL", temporal)
@@ -376,6 +376,29 @@ def test_kernel_selection_rules(monkeypatch):
     m = c.Model(c.cavity_grid(1024), p)
     assert m.kernel_config == {"fastdiv": 0, "temporal": 4} and m.jacobi_kernel["kind"] == 4
     m.close()
+
+
+def test_unknown_tb_kind_is_rejected(monkeypatch):
+    """CFD_TB_KIND names a march there is; any other value (3 named a kernel
+    that no longer exists; 7 never named one) fails model creation with
+    CFD_EINVAL and a message naming the knob, instead of selecting kind 1
+    silently.  4 and 5 are created and report their kind.  (Kind 1 still
+    exists and is still accepted; test_kernel_variants_bitwise runs it.)"""
+    c = _cfd()
+    from cfdamd._lib import CFD_EINVAL
+    grid = c.cavity_grid(32, 16)
+    p = c.SimulationParams.cavity(100.0, 50, corrector_passes=0, tol_enabled=False)
+    for kind in ("3", "7"):
+        monkeypatch.setenv("CFD_TB_KIND", kind)
+        with pytest.raises(c.CfdError) as e:
+            c.Model(grid, p)
+        assert e.value.code == CFD_EINVAL
+        assert "CFD_TB_KIND" in str(e.value)
+    for kind in ("4", "5"):
+        monkeypatch.setenv("CFD_TB_KIND", kind)
+        m = c.Model(grid, p)
+        assert m.jacobi_kernel["kind"] == int(kind), m.jacobi_kernel
+        m.close()
 
 
 @pytest.mark.timeout(300)

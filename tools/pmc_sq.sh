@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box: SQ instruction/cycle counters of the Jacobi kernel only, one short
 # run per launch geometry.  Usage: bash tools/pmc_sq.sh TAG "kind,T,R;..."
+# (kind 1, 4 or 5, as CFD_TB_KIND)
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp TB_WARMUP=${TB_WARMUP:-2}
 TAG=$1

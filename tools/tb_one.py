@@ -1,5 +1,5 @@
-"""One model, one launch geometry (CFD_TB_KIND / CFD_TEMPORAL / CFD_TB_ROWS /
-CFD_XCD_REMAP from the environment) on the bench workload, in its own
+"""One model, one launch geometry (CFD_TB_KIND 1, 4 or 5 / CFD_TEMPORAL /
+CFD_TB_ROWS / CFD_XCD_REMAP from the environment) on the bench workload, in its own
 process: prints one JSON line with the solve time per sweep and the step time.
 Also the unit rocprofv3 PMC passes attach to.  Usage: tb_one.py [n] [steps]
 n: N (N x N cavity) or NXxNY[@S]: an NX x NY cavity-type grid with spacing 1/S

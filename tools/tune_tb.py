@@ -1,6 +1,8 @@
 """Sweep Jacobi launch geometries on the GPU, one fresh process per config
 (tools/tb_one.py on the bench workload), two passes, best of the two.
-TUNE_CONFIGS="kind,T,R[,xcd];..." overrides the list.  Usage: tune_tb.py [n]"""
+TUNE_CONFIGS="kind,T,R[,xcd];..." overrides the list (kind 1: register rings, T <= 4; 4: the register
+pipeline; 5: the march with its rhs window in LDS; R <= 0: balanced segments
+at -R blocks per CU).  Usage: tune_tb.py [n]"""
 import json
 import os
 import subprocess
@@ -8,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 n = sys.argv[1] if len(sys.argv) > 1 else "4096"
-configs = [(1, 4, 24), (3, 6, 24), (3, 8, 24)]
+configs = [(4, 4, 24), (4, 8, 24), (5, 8, -3)]
 if os.environ.get("TUNE_CONFIGS"):
     configs = [tuple(int(x) for x in c.split(",")) for c in os.environ["TUNE_CONFIGS"].split(";")]
 configs = [c if len(c) == 4 else tuple(c) + (1,) for c in configs]
