@@ -466,6 +466,16 @@ class Model:
         return int(n.value)
 
     @property
+    def sums_bounds(self) -> dict:
+        """The fma form's guard words as they stand (cfd_get_sums_bounds):
+        state 0 / 1 / 2 and the bounds of max |p'| (m0) and max |rhs| (rm) as
+        f32 bits with the sign cleared; zeros where the model keeps none."""
+        s, a, b = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check("cfd_get_sums_bounds",
+              load().cfd_get_sums_bounds(self._hh(), C.byref(s), C.byref(a), C.byref(b)))
+        return {"state": int(s.value), "m0": int(a.value), "rm": int(b.value)}
+
+    @property
     def comm_calls(self) -> int:
         """Halo-exchange groups + all-reduces enqueued (cfd_get_comm_calls)."""
         n = C.c_uint64()

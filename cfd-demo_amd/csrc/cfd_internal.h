@@ -350,6 +350,9 @@ void launch_boundary(const Geom &g, const Fields &f, hipStream_t s);
 // access (nx % 4 == 0, 16-byte aligned arrays), else the scalar form.
 void launch_correct_finish(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
 void launch_step_reduce(const Geom &g, const Fields &f, hipStream_t s);
+// max |p'| bound of the fma form's guard after a step with corrector passes
+// (k_correct_finish4m publishes it itself); Fields::sums_track only
+void launch_publish_sums_m0(const Geom &g, const Fields &f, hipStream_t s);
 // The corrector of pass `pass` and, when pass+1 exists (has_next) and the
 // device's go flag says it runs, pass+1's head (u* <- u, v* <- v,
 // divergence) in one launch (k_correct_head4, single domain; every pass of the

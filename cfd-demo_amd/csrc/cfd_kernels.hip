@@ -1074,6 +1074,27 @@ __global__ void k_abort_from_red(Fields f) {
         __hip_atomic_store(f.host_nonfinite + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The fma form's p' bound (Ctl::sums_m0, sums_state 0 -> 1) for a step that
+// does not end in k_correct_finish4m -- one with corrector passes, whose last
+// corrector is k_correct_head4: the same words the finish publishes, from one
+// pass over the owned rows of the p' the last solve left (the word is zero
+// since that solve's finalize).  Only launched where Fields::sums_track is set.
+__global__ __launch_bounds__(kBlock) void k_publish_sums_m0(Geom g, Fields f) {
+    Ctl *c = f.ctl;
+    const float *__restrict__ pp = c->cur ? f.pp[1] : f.pp[0];
+    const size_t n = (size_t)g.nx * (size_t)g.nyl;
+    uint32_t pm = 0u;
+    for (size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (size_t)gridDim.x * kBlock)
+        pm = max(pm, abs_bits(pp[k]));
+    const uint32_t thr = __float_as_uint(kSumsPLim * g.dx_sq);   // 2^122 / R, exact
+    raise_bits_bound(&c->sums_m0, pm, thr);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicMax(&c->sums_m0, thr);
+        c->sums_rm = 0u;
+        c->sums_state = 1u;
+    }
+}
+
 __global__ void k_step_finalize(Geom g, Fields f) { step_finalize_body(g, f); }
 
 // One row of k_correct_finish4m's work for the 4 columns i0..i0+3 of local
@@ -1550,6 +1571,11 @@ void launch_boundary(const Geom &g, const Fields &f, hipStream_t s) {
 void launch_step_reduce(const Geom &g, const Fields &f, hipStream_t s) {
     const size_t n = (size_t)(g.nyl + 1) * (g.nx + 1);
     hipLaunchKernelGGL(k_step_reduce, dim3(copy_grid(n / 4 + 1)), dim3(kBlock), 0, s, g, f);
+}
+
+void launch_publish_sums_m0(const Geom &g, const Fields &f, hipStream_t s) {
+    const size_t n = (size_t)g.nx * (size_t)g.nyl;
+    hipLaunchKernelGGL(k_publish_sums_m0, dim3(copy_grid(n)), dim3(kBlock), 0, s, g, f);
 }
 
 void launch_abort_to_red(const Fields &f, hipStream_t s) {

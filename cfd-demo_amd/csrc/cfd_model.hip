@@ -1769,6 +1769,9 @@ struct cfd_model {
         rc = enqueue_piso(kNaN, fused);
         if (rc) return rc;
         if (!fused) launch_step_reduce(g, f, stream);
+        // a step with corrector passes ends in k_correct_head4, which publishes
+        // no max |p'|: bound the p' the next step's first solve starts from
+        if (!fused && f.sums_track) launch_publish_sums_m0(g, f, stream);
         if (sharded()) launch_fold_slots(f.ctl->red, f.red_slots, 4, stream);
         // slabs with persistent runs: a rank whose persistent solve timed out
         // tells every rank through the step all-reduce (red[6])
@@ -3139,6 +3142,20 @@ int cfd_get_sums_launches(cfd_model *m, uint64_t *launches) {
     int rc = m->read_ctl(&c);
     if (rc) return rc;
     *launches = c.sums_launches;   // per-launch marches run in the fma form
+    return 0;
+}
+
+int cfd_get_sums_bounds(cfd_model *m, uint32_t *state, uint32_t *m0_bits, uint32_t *rm_bits) {
+    if (!m || !state || !m0_bits || !rm_bits) return fail(CFD_EINVAL, "null argument");
+    Ctl c;
+    int rc = m->read_ctl(&c);
+    if (rc) return rc;
+    // the fma form's guard words as the next solve would read them; a model
+    // that never keeps them (Fields::sums_track 0) reports zeros
+    const bool on = m->f.sums_track != 0;
+    *state = on ? c.sums_state : 0u;
+    *m0_bits = on ? c.sums_m0 : 0u;
+    *rm_bits = on ? c.sums_rm : 0u;
     return 0;
 }
 

@@ -273,6 +273,15 @@ int cfd_get_persist_sums(cfd_model *m, uint64_t *blocks);
  * finish and the predictor march publish, summed over the model's life.
  * CFD_JACOBI_SUMS=0 keeps it at 0.  Synchronises.  (new; diagnostics) */
 int cfd_get_sums_launches(cfd_model *m, uint64_t *launches);
+/* The words that guard reads, as they stand now: state (0 nothing valid, 1 the
+ * corrector finish bounded the p' the next solve starts from, 2 the predictor
+ * march bounded its rhs as well), and the bounds of max |p'| and max |rhs| as
+ * f32 bits with the sign cleared (NaN and Inf compare above every finite
+ * value).  Each bound is at least its threshold (2^122 dx^2, 2^112) once
+ * published.  All zero for a model that never keeps them (sharded, another
+ * solver, the tolerance on, a grid without the form, CFD_JACOBI_SUMS=0).
+ * Read-only; synchronises.  (new; diagnostics) */
+int cfd_get_sums_bounds(cfd_model *m, uint32_t *state, uint32_t *m0_bits, uint32_t *rm_bits);
 /* Collective calls this (sharded) model has enqueued: halo-exchange groups
  * and all-reduces, summed over its life (0 unsharded).  (new; diagnostics) */
 int cfd_get_comm_calls(const cfd_model *m, uint64_t *n);

@@ -136,9 +136,11 @@ def test_guard_falls_back(name):
     own tests below).  nan / inf: the first step after set_state runs the
     reference's body whatever the maxima, and after it the model refuses to
     step on (non-finite velocities), so the kernel's own answer to NaN / Inf
-    maxima -- `bound < 2^123` is false for a NaN or Inf sum -- cannot be
-    reached through update(); these two cases pin the step the model still
-    runs and that the counter stands still."""
+    maxima -- `bound < 2^123` is false for a NaN or Inf sum -- is not seen
+    through update() and the counter alone; these two cases pin the step the
+    model still runs and that the counter stands still.  What the publishers
+    answer to a NaN or Inf in p' is read back (Model.sums_bounds) in
+    test_gpu_sums_fma_shapes.py::test_finish_maximum_sees_the_planted_cell."""
     import cfdamd
     nx, ny = SHAPES[0]
     m, o, _ = _pair(nx, ny)
