@@ -136,6 +136,47 @@ def nonfinite_share(arrays):
     return max(float(np.count_nonzero(~np.isfinite(a))) / a.size for a in arrays)
 
 
+# inputs of the SOR / multigrid seam tests (test_gpu_solver_seams.py on the
+# device, test_oracle_solvers.py for their premises with the oracle alone)
+
+SPACINGS = ("pow2", "div")
+# (nx, ny) of the NaN-ignoring final residual: lx = 8, ly = 1, one and two levels
+SHALLOW_NAN_GRIDS = [(1024, 4), (2048, 4), (2048, 5)]
+SHALLOW_LX, SHALLOW_LY = 8.0, 1.0
+
+
+def spacing(nx, ny, kind):
+    """(lx, ly): pow2 gives dx = dy = 2^-7 (every division of the solvers by a
+    grid constant becomes a multiply by its exact reciprocal), div a 30 x 10
+    domain (IEEE double division)."""
+    assert kind in SPACINGS, kind
+    return (nx / 128.0, ny / 128.0) if kind == "pow2" else (30.0, 10.0)
+
+
+def solver_rhs(nx, ny, flavour, scale=None):
+    """rhs of a pressure solve from adversarial_state's per-field generator:
+    `signs` times 50 (as the large multigrid grids), `range` as it is."""
+    rhs = adversarial_state(nx, ny, 1, flavour)["rhs"]
+    if scale is None:
+        scale = 50.0 if flavour == "signs" else 1.0
+    return (rhs * np.float32(scale)).astype(np.float32)
+
+
+def with_boundary_nan(rhs, nx, ny):
+    """A copy with NaN on every boundary cell (neither solver may read them)."""
+    r = rhs.reshape(ny, nx).copy()
+    r[0, :] = r[ny - 1, :] = np.nan
+    r[:, 0] = r[:, nx - 1] = np.nan
+    return r.ravel()
+
+
+def shallow_nan_rhs(nx, ny):
+    """uniform(-1, 1) with one NaN at (nx / 2, 1)."""
+    rhs = np.random.default_rng([nx, ny, 77]).uniform(-1, 1, nx * ny).astype(np.float32)
+    rhs[nx // 2 + nx] = np.nan
+    return rhs
+
+
 # planted-spike states of the Jacobi residual tests
 
 SPIKE_NOISE = 1e-3

@@ -11,7 +11,11 @@ and outputs as small fixtures tests/golden/js_mg_*.npz.  No reference source
 is written to the repository: only the numbers.  The GPU path and the C
 restatement (oracle/cfd_oracle_solvers.c) must reproduce them bit for bit.
 
-    python tests/golden/make_js_golden.py
+    python tests/golden/make_js_golden.py [NAME ...]
+
+Only fixtures whose .npz is missing are generated (all of CASES, or only the
+NAMEs given); the committed ones and their manifest entries stay as they are.
+New cases are appended to CASES: the seed of a case is 4242 + its position.
 """
 import json
 import os
@@ -30,6 +34,17 @@ CASES = {
     "js_mg_128x128": (128, 128, 1.0, 1.0),            # power-of-two spacing (cavity)
     "js_mg_136x72": (136, 72, 30.0, 10.0),            # odd coarse sizes (17, 9, 5, 3)
     "js_mg_40x24": (40, 24, 30.0, 10.0),              # shallow hierarchy
+    # one level (ny <= 4): mgVcycle is its 10 coarse smooths after the 5 pre-smooths
+    "js_mg_16x4": (16, 4, 16 / 128.0, 4 / 128.0),
+    "js_mg_16x4_div": (16, 4, 30.0, 10.0),
+    # two levels: 16x5 -> 8x3
+    "js_mg_16x5": (16, 5, 16 / 128.0, 5 / 128.0),
+    "js_mg_16x5_div": (16, 5, 30.0, 10.0),
+    # odd ny on the finest level, odd coarse sizes in both directions
+    "js_mg_24x7": (24, 7, 24 / 128.0, 7 / 128.0),     # 12x4
+    "js_mg_56x15": (56, 15, 30.0, 10.0),              # 28x8, 14x4
+    "js_mg_104x29": (104, 29, 104 / 128.0, 29 / 128.0),   # 52x15, 26x8, 13x4
+    "js_mg_216x57": (216, 57, 30.0, 10.0),            # 108x29, 54x15, 27x8, 14x4
 }
 
 HARNESS = r"""
@@ -75,18 +90,31 @@ def extract():
     return fns, html[c0:c1]
 
 
-def main():
+def main(only=()):
+    unknown = [n for n in only if n not in CASES]
+    if unknown:
+        raise SystemExit(f"unknown fixture(s) {unknown}; CASES has {list(CASES)}")
     fns, branch = extract()
     for name in ("mgSmooth", "mgRestrict", "mgProlongate", "mgVcycle"):
         assert f"function {name}(" in fns, name
     assert "mgVcycle(pPrime, rhs, Nx, Ny, dx, dy)" in branch
-    manifest = {"generator": "tests/golden/make_js_golden.py",
-                "source": "reference index.html:1344-1470 (mg*), :775-795 (multigrid branch), "
-                          "executed by node " + subprocess.run(["node", "--version"],
-                                                               capture_output=True,
-                                                               text=True).stdout.strip(),
-                "fixtures": {}}
+    mpath = os.path.join(HERE, "js_manifest.json")
+    if os.path.exists(mpath):
+        manifest = json.load(open(mpath))
+    else:
+        manifest = {"generator": "tests/golden/make_js_golden.py",
+                    "source": "reference index.html:1344-1470 (mg*), :775-795 (multigrid branch), "
+                              "executed by node " + subprocess.run(["node", "--version"],
+                                                                   capture_output=True,
+                                                                   text=True).stdout.strip(),
+                    "fixtures": {}}
     for k, (name, (nx, ny, lx, ly)) in enumerate(CASES.items()):
+        if only and name not in only:
+            continue
+        if os.path.exists(os.path.join(HERE, name + ".npz")):
+            assert name in manifest["fixtures"], f"{name}.npz has no manifest entry"
+            print(name, "kept")
+            continue
         dx = np.float32(lx) / np.float32(nx)
         dy = np.float32(ly) / np.float32(ny)
         rng = np.random.default_rng(4242 + k)
@@ -113,8 +141,8 @@ def main():
         manifest["fixtures"][name] = {"nx": nx, "ny": ny, "lx": lx, "ly": ly,
                                       "dx": float(dx), "dy": float(dy), "seed": 4242 + k}
         print(name, "residual", res)
-    json.dump(manifest, open(os.path.join(HERE, "js_manifest.json"), "w"), indent=1)
+    json.dump(manifest, open(mpath, "w"), indent=1)
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))

@@ -16,7 +16,8 @@ import os
 import numpy as np
 import pytest
 
-from _util import assert_bitwise
+from _util import (assert_bitwise, nonfinite_share, SHALLOW_LX, SHALLOW_LY, SHALLOW_NAN_GRIDS,
+                   shallow_nan_rhs, solver_rhs, spacing, with_boundary_nan)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
@@ -92,6 +93,13 @@ def np_sor(rhs, nx, ny, dx, dy, iters, tol_enabled, p_tol):
     (48, 40, 30.0, 10.0, 200, True, 1e-2),
     (64, 64, 1.0, 1.0, 7, True, 10.0),
     (16, 4, 1.0, 1.0, 5, False, 1.0),
+] + [
+    # two wave columns of the device's fused form (2 x 124 columns) and its row
+    # categories: ny - 2 = 15 (below the fused form), 16 and 32 (one segment),
+    # 31 and 33 (two overlapping segments); both spacing kinds, tolerance off / on
+    (248, ny, lx, ly, 7, tol, 1.0)
+    for ny in (17, 18, 33, 34, 35)
+    for lx, ly, tol in ((248 / 128.0, ny / 128.0, False), (30.0, 10.0, True))
 ])
 def test_red_black_sor_matches_numpy(nx, ny, lx, ly, iters, tol, scale):
     o = _orc()
@@ -106,6 +114,49 @@ def test_red_black_sor_matches_numpy(nx, ny, lx, ly, iters, tol, scale):
     assert_bitwise("sor p'", pp, want)
     if tol and iters == 200:
         assert n < iters   # converged and stopped early
+
+
+MAX_NONFINITE_SHARE = 0.20   # as tests/test_gpu_adversarial.py
+
+
+@pytest.mark.parametrize("nx,ny", SHALLOW_NAN_GRIDS)
+def test_shallow_multigrid_nan_stays_local(nx, ny):
+    """Premise of the device's NaN-ignoring final residual test: on a hierarchy
+    of one or two levels one NaN in rhs spoils a small share of the multigrid
+    result, and the residual (the maximum over the cells it has not reached)
+    is finite and positive."""
+    o = _orc()
+    rhs = shallow_nan_rhs(nx, ny)
+    assert np.count_nonzero(np.isnan(rhs)) == 1 and np.isnan(rhs[nx // 2 + nx])
+    pp = np.empty(nx * ny, np.float32)
+    dx, dy = np.float32(SHALLOW_LX) / np.float32(nx), np.float32(SHALLOW_LY) / np.float32(ny)
+    r = np.float32(o.mg_solve(pp, rhs, nx, ny, dx, dy))
+    share = nonfinite_share([pp])
+    print(f"{nx}x{ny}: non-finite share {share:.4f}, residual {r!r}")
+    assert 0.0 < share <= MAX_NONFINITE_SHARE, share
+    assert np.isfinite(r) and r > 0.0, r
+
+
+@pytest.mark.parametrize("kind", ["pow2", "div"])
+@pytest.mark.parametrize("nx,ny", [(56, 15), (216, 29), (248, 35)])
+def test_boundary_rhs_cells_are_never_read(nx, ny, kind):
+    """NaN on every boundary rhs cell leaves both solvers' results as they are
+    without it: no non-finite word, the same bits, the same residual."""
+    o = _orc()
+    lx, ly = spacing(nx, ny, kind)
+    dx, dy = np.float32(lx) / np.float32(nx), np.float32(ly) / np.float32(ny)
+    rhs = solver_rhs(nx, ny, "signs")
+    spoilt = with_boundary_nan(rhs, nx, ny)
+    assert np.count_nonzero(np.isnan(spoilt)) == 2 * nx + 2 * ny - 4
+    for solve in (lambda pp, r: (o.mg_solve(pp, r, nx, ny, dx, dy), 1),
+                  lambda pp, r: o.sor_solve(pp, r, nx, ny, dx, dy, 7, False, 1e-4),
+                  lambda pp, r: o.sor_solve(pp, r * np.float32(1e-2), nx, ny, dx, dy, 400, True, 1e-4)):
+        a, b = np.empty(nx * ny, np.float32), np.empty(nx * ny, np.float32)
+        ra, na = solve(a, rhs)
+        rb, nb = solve(b, spoilt)
+        assert nonfinite_share([b]) == 0.0
+        assert_bitwise(f"{nx}x{ny} {kind}", b, a)
+        assert np.isfinite(rb) and np.float32(ra) == np.float32(rb) and na == nb
 
 
 def test_model_dispatches_selected_solver():
