@@ -50,6 +50,8 @@ class PressureSolver(enum.IntEnum):          # model.rs:148-152
     # the JavaScript variant's solvers (index.html:741-774, 775-795, 1344-1470)
     Sor = 1
     Multigrid = 2
+    # the script's SOR in the script's own order (in place, row by row), one domain only
+    SorLex = 4                               # 3 is unassigned (CFD_EINVAL, as before)
 
 
 class VisualizationMode(enum.IntEnum):       # app.rs:505-509

@@ -129,6 +129,15 @@ __device__ __forceinline__ float sdiv(float x, float c, float r) {
     return SP ? x * r : x / c;
 }
 
+// x / c in the script's double arithmetic (cfd_solvers.hip, cfd_sor_lex.hip).
+// FAST is a template parameter: with a runtime flag the compiler if-converts
+// and evaluates the ~30-instruction IEEE f64 division sequence on both paths.
+template <int FAST>
+__device__ __forceinline__ double ddiv(double x, double c, double r) {
+    if (FAST) return x * r;
+    return x / c;
+}
+
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 template <int FAST>

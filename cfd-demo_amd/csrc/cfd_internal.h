@@ -319,6 +319,18 @@ void launch_sor_fused(float *pa, float *pb, const float *rhs, int nx, int ny, co
                       Ctl *ctl, uint32_t *err_slots, int pass, int it, int tol, float p_tol, int res,
                       int row_lo, int row_hi, int j0, int lo_clamp, int hi_clamp, hipStream_t s);
 void launch_fill_zero(float *p, size_t n, const Ctl *ctl, int pass, hipStream_t s);
+// SOR in the script's own order (cfd_sor_lex.hip, pressure_solver 4): the
+// whole solve as one launch of (iteration, 64-row band) tasks handed out by a
+// ticket counter, plus, with the tolerance on, a replay launch that returns
+// at once unless iterations had run past the early exit.  Iteration k reads
+// buffer (ctl->cur + k) & 1 and writes the other (k = 0 reads nothing), and
+// folds its max |new - old| into ctl->err[k]: the caller's finalize flips the
+// buffer once per iteration run.  pol: sor_lex_words(iters, ny) words the
+// launcher zeroes before each launch; exitw: 4 words.  iters >= 1.
+size_t sor_lex_words(int iters, int ny);
+hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
+                          Ctl *ctl, uint32_t *pol, uint32_t *exitw, uint32_t *host_fail, int pass,
+                          int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s);
 void launch_mg_smooth(const MgLevel &L, const float *src, float *dst, const Ctl *ctl, int pass,
                       hipStream_t s);
 // Five smoothing sweeps src -> dst in one launch (temporal blocking: one

@@ -643,6 +643,44 @@ struct cfd_model {
         return 0;
     }
 
+    // SOR in the script's own order (index.html:741-774; cfd_sor_lex.hip):
+    // one ticketed launch for the whole solve, a replay launch behind it with
+    // the tolerance on.  The buffers flip once per iteration run, as in the
+    // fused red-black solve; one domain only (validate_sharded).
+    uint32_t *lex_pol = nullptr, *lex_exit = nullptr;
+    size_t lex_words = 0;
+    int enqueue_sor_lex(int pass) {
+        const int iters = params.jacobi_iters;
+        if (sharded()) return fail(CFD_EINVAL, "pressure_solver 4 (script-order SOR) runs on one domain only");
+        hipEvent_t e0;
+        begin_solve_timing(pass, &e0);
+        int launches = 0;
+        if (iters < 1) {
+            // p' = 0 (index.html:743) in whichever buffer is current
+            launch_fill_zero(f.pp[0], (size_t)g.nx * g.ny, f.ctl, pass, stream);
+            launch_fill_zero(f.pp[1], (size_t)g.nx * g.ny, f.ctl, pass, stream);
+            launches = 2;
+        } else {
+            const size_t need = sor_lex_words(iters, g.ny);
+            if (need > lex_words) {
+                if (lex_pol) HIP_TRY(hipFree(lex_pol));   // waits for the device
+                lex_pol = nullptr;
+                lex_words = 0;
+                HIP_TRY(hipMalloc((void **)&lex_pol, need * 4));
+                lex_words = need;
+            }
+            if (!lex_exit) HIP_TRY(hipMalloc((void **)&lex_exit, 16));
+            HIP_TRY(launch_sor_lex(f.pp[0], f.pp[1], f.rhs, g.nx, g.ny, sor_consts(), f.ctl, lex_pol,
+                                   lex_exit, f.host_nonfinite ? f.host_nonfinite + 2 : nullptr, pass,
+                                   iters, g.tol_enabled, g.p_tol, g.n_cu, &launches, stream));
+        }
+        end_solve_timing(e0, (uint64_t)iters, (uint64_t)launches);
+        launch_finalize_solve(g, f, pass, iters, pass >= 1 ? 1 : 0, iters, stream);
+        if (!g.tol_enabled) host_cur = (host_cur + iters) & 1;
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+
     // Level table of mgVcycle's recursion: sizes floor((n+1)/2) down to the
     // first level with nx <= 4 or ny <= 4 (index.html:1444-1451), spacing
     // doubling per level (:1458).
@@ -1122,6 +1160,7 @@ struct cfd_model {
     int enqueue_solve(int pass) {
         if (params.pressure_solver == CFD_SOLVER_SOR) return enqueue_sor(pass);
         if (params.pressure_solver == CFD_SOLVER_MULTIGRID) return enqueue_mg(pass);
+        if (params.pressure_solver == CFD_SOLVER_SOR_LEX) return enqueue_sor_lex(pass);
         const int iters = params.jacobi_iters;
         const int lo_g = 1 - (int)j0, hi_g = (int)g.ny - 1 - (int)j0;   // global rows 1..ny-2
         bool evt = timing && pass <= 0;
@@ -1884,6 +1923,14 @@ struct cfd_model {
     int persist_timeout_check(bool at_sync) {
         if (!h_nonfinite || !*(volatile uint32_t *)(h_nonfinite + 2)) return 0;
         if (!at_sync && sharded()) return 0;
+        if (params.pressure_solver == CFD_SOLVER_SOR_LEX) {
+            // no checkpoint is kept for this solver: p' is invalid until cfd_set_state
+            HIP_TRY(hipStreamSynchronize(stream));
+            *(volatile uint32_t *)(h_nonfinite + 2) = 0u;
+            clear_abort_words();
+            return fail(CFD_ETIMEOUT, "script-order SOR solve timed out waiting for a workgroup; "
+                                      "its result is invalid until cfd_set_state");
+        }
         const char *which = last_abort_resident ? "resident tolerance-mode" : "persistent";
         HIP_TRY(hipStreamSynchronize(stream));
         if (cstream) HIP_TRY(hipStreamSynchronize(cstream));
@@ -2033,7 +2080,7 @@ struct cfd_model {
                           (void *)us_all, (void *)vs_all, (void *)p, (void *)rhs,
                           (void *)pp_all[0], (void *)pp_all[1], (void *)mask_u, (void *)mask_v,
                           (void *)obs, (void *)ctl, (void *)slots, (void *)vis_buf,
-                          (void *)mg_pool, (void *)mg_dev})
+                          (void *)mg_pool, (void *)mg_dev, (void *)lex_pol, (void *)lex_exit})
             if (ptr) (void)hipFree(ptr);
         if (h_nonfinite) (void)hipHostFree(h_nonfinite);
         if (ck_pool) (void)hipFree(ck_pool);
@@ -2070,8 +2117,11 @@ int validate(const cfd_grid *grid, const cfd_params *p) {
         return fail(CFD_EINVAL, "velocity_scheme must be 0 or 1");
     if (p->inlet_profile != 0 && p->inlet_profile != 1)
         return fail(CFD_EINVAL, "inlet_profile must be 0 or 1");
-    if (p->pressure_solver < CFD_SOLVER_JACOBI || p->pressure_solver > CFD_SOLVER_MULTIGRID)
-        return fail(CFD_EINVAL, "pressure_solver must be 0 (Jacobi), 1 (SOR) or 2 (multigrid)");
+    // 3 is unassigned: it was rejected before CFD_SOLVER_SOR_LEX existed and stays so
+    if (p->pressure_solver < CFD_SOLVER_JACOBI || p->pressure_solver > CFD_SOLVER_SOR_LEX ||
+        p->pressure_solver == 3)
+        return fail(CFD_EINVAL, "pressure_solver must be 0 (Jacobi), 1 (SOR), 2 (multigrid) or "
+                                "4 (SOR in the script's order)");
     if (p->bc_kind != 0 && p->bc_kind != 1) return fail(CFD_EINVAL, "bc_kind must be 0 or 1");
     return 0;
 }
@@ -2081,6 +2131,9 @@ int validate(const cfd_grid *grid, const cfd_params *p) {
 // chosen (create, cfd_set_params, cfd_run_set_params), so a step never fails
 // half-way through with u*, v* and rhs already written.
 int validate_sharded(const cfd_model *m, const cfd_params *p) {
+    if (m->n_ranks > 1 && p->pressure_solver == CFD_SOLVER_SOR_LEX)
+        return fail(CFD_EINVAL, "pressure_solver 4 (SOR in the script's order) runs on one domain "
+                                "only: sharded models take 0, 1 or 2");
     if (m->n_ranks <= 1 || p->pressure_solver != CFD_SOLVER_SOR) return 0;
     const int lo = std::max(0, 1 - (int)m->j0);
     const int hi = std::min((int)(m->j1 - m->j0), (int)m->grid.ny - 1 - (int)m->j0);
@@ -2485,6 +2538,9 @@ int create_common(const cfd_grid *grid, const cfd_params *params, int device, in
     int rc = validate(grid, params);
     if (rc) return rc;
     if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(CFD_EINVAL, "bad rank/n_ranks");
+    if (n_ranks > 1 && params->pressure_solver == CFD_SOLVER_SOR_LEX)   // before any device call
+        return fail(CFD_EINVAL, "pressure_solver 4 (SOR in the script's order) runs on one domain "
+                                "only: sharded models take 0, 1 or 2");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(CFD_EHIP, "no HIP device available");

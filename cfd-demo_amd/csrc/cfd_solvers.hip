@@ -24,15 +24,6 @@
 namespace cfd {
 namespace {
 
-// x / c in the script's double arithmetic.  FAST is a template parameter:
-// with a runtime flag the compiler if-converts and evaluates the ~30-instruction
-// IEEE f64 division sequence on both paths.
-template <int FAST>
-__device__ __forceinline__ double ddiv(double x, double c, double r) {
-    if (FAST) return x * r;
-    return x / c;
-}
-
 // ------------------------------------------------------------------- SOR
 
 // One color of red-black SOR over the interior i = 1..nx-2, j = 1..ny-2

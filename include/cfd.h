@@ -103,8 +103,30 @@ enum { CFD_INLET_UNIFORM = 0, CFD_INLET_PARABOLIC = 1 };
  * whose every slab boundary divides by 2^(l+1) (>= 16 rows per slab there)
  * are partitioned -- each rank smooths, forms residuals and restricts only
  * its rows, with 8-row ghost exchanges per level -- and the coarser levels
- * are gathered and solved whole on every rank. */
-enum { CFD_SOLVER_JACOBI = 0, CFD_SOLVER_SOR = 1, CFD_SOLVER_MULTIGRID = 2 };
+ * are gathered and solved whole on every rank.
+ * SOR_LEX (value 4; 3 is unassigned and stays rejected with CFD_EINVAL, as
+ * before this solver existed) is the script's SOR in the script's own order
+ * (index.html:741-774):
+ * p' restarts from 0 and is updated in place, row by row, left to right,
+ * omega 1.7, in double with f32 stores, then rows 0 / ny-1 and columns 0 /
+ * nx-1 are copied as :761-770 does; the iterates are the script's bit for bit
+ * (tests/golden/js_sor_*.npz hold the script's own results under node).  It
+ * runs jacobi_iters iterations with the early exit at p_tol when tol_enabled,
+ * reports (float)maxError of the last iteration run, and jacobi_sweeps_total
+ * grows by the iterations run -- the conventions of CFD_SOLVER_SOR.  The one
+ * place its arithmetic can differ from the script: the script compares the
+ * double maxError with the double 1e-4, this library (float)maxError with the
+ * float p_tol, as CFD_SOLVER_SOR does; the two disagree only when maxError
+ * falls in the sliver just below 1e-4 that rounds to or above f32(1e-4).
+ * One domain only: cfd_create_sharded* and a cfd_set_params on a sharded
+ * model return CFD_EINVAL for it.  On the GPU it is a pipelined wavefront of
+ * (iteration, 64-row band) tasks in one launch (cfd_sor_lex.hip);
+ * CFD_SOR_LEX_WGS=N caps its workgroups (any N >= 1 gives the same bits).  Its
+ * waits are bounded like the persistent Jacobi solve's
+ * (CFD_PERSIST_DEADLINE_US): past the deadline the next synchronising call
+ * returns CFD_ETIMEOUT and p' is invalid until cfd_set_state (no checkpoint
+ * is kept for this solver). */
+enum { CFD_SOLVER_JACOBI = 0, CFD_SOLVER_SOR = 1, CFD_SOLVER_MULTIGRID = 2, CFD_SOLVER_SOR_LEX = 4 };
 enum { CFD_BC_CHANNEL = 0, CFD_BC_CAVITY = 1 };
 typedef struct {
     float dt;
