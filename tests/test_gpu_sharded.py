@@ -10,6 +10,7 @@ import threading
 import numpy as np
 import pytest
 
+from _slabs import _slab_slices, assemble, run_sharded_from_state  # noqa: F401 (re-exported)
 from _util import assert_bitwise
 
 pytestmark = pytest.mark.gpu
@@ -56,25 +57,6 @@ def run_sharded(n, grid, params, steps, halo_depth, geoms=None, extra=None):
     if extra is not None:
         return states, extras
     return states
-
-
-def assemble(states, nx):
-    """Owned rows of every slab -> global flat arrays (v gets the top face
-    from the last slab)."""
-    out = {}
-    for f in ("u", "p", "p_prime", "u_star", "rhs"):
-        out[f] = np.concatenate([s[f] for (_, _, s, _) in states])
-    for f in ("v", "v_star"):
-        parts = []
-        for k, (j0, j1, s, _) in enumerate(states):
-            rows = s[f].reshape(j1 - j0 + 1, nx)
-            parts.append(rows if k == len(states) - 1 else rows[:-1])
-            if k < len(states) - 1:
-                # the shared face row is held (and computed) by both ranks
-                nxt = states[k + 1][2][f].reshape(-1, nx)[0]
-                assert_bitwise(f"{f} shared face row {j1}", rows[-1], nxt)
-        out[f] = np.concatenate(parts).ravel()
-    return out
 
 
 def check_against_oracle(states, grid, oracle_kw, steps, fields):
@@ -278,52 +260,6 @@ def test_sharded_multigrid_matches_oracle(monkeypatch, n, tol, smooth):
     st = run_sharded(n, grid, params, 4, 4)
     check_against_oracle(st, grid, dict(pressure_solver=2, corrector_passes=3,
                                         tol_enabled=int(tol)), 4, FIELDS + ("rhs",))
-
-
-def _slab_slices(st, nx, j0, j1):
-    out = {}
-    for k in ("u", "u_star"):
-        out[k] = st[k].reshape(-1, nx + 1)[j0:j1].ravel().copy()
-    for k in ("v", "v_star"):
-        out[k] = st[k].reshape(-1, nx)[j0:j1 + 1].ravel().copy()
-    for k in ("p", "p_prime", "rhs"):
-        out[k] = st[k].reshape(-1, nx)[j0:j1].ravel().copy()
-    for k in ("dt", "simulation_time", "simulation_step", "last_p_residual", "last_u_residual",
-              "last_v_residual", "jacobi_sweeps_total"):
-        out[k] = st[k]
-    return out
-
-
-def run_sharded_from_state(n, grid, params, state, steps):
-    """LocalHub slabs started from a single-domain state (cfd_set_state on
-    every slab, collective: it exchanges the ghosts)."""
-    import cfdamd
-    hub = cfdamd.LocalHub(n)
-    states, models, errors = [None] * n, [None] * n, []
-
-    def worker(r):
-        try:
-            m = cfdamd.Model(grid, params, device=0, n_ranks=n, rank=r, local_hub=hub)
-            models[r] = m
-            m.set_state(**_slab_slices(state, grid.nx, m.j0, m.j1))
-            m.update_n(steps)
-            m.synchronize()
-            states[r] = (m.j0, m.j1, m.get_state(), m.halo_depth)
-        except Exception as e:   # surfaced below
-            errors.append(e)
-
-    ts = [threading.Thread(target=worker, args=(r,), daemon=True) for r in range(n)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(900)
-    for m in models:
-        if m is not None:
-            m.close()
-    hub.close()
-    if errors:
-        raise errors[0]
-    return states
 
 
 @pytest.mark.timeout(600)
