@@ -214,6 +214,11 @@ def _fp(a: Optional[np.ndarray]):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _dp(a: np.ndarray):
+    assert a.dtype == np.float64 and a.flags.c_contiguous
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
 class Model:
     """`Model` (model.rs:166-214) with its fields resident in HBM."""
 
@@ -519,6 +524,54 @@ class Model:
     def halo_depth(self) -> int:
         return int(load().cfd_get_halo_depth(self._hh()))
 
+    # -------------------------------------------------------------- tracers
+    def tracers_enable(self, capacity: int, interval: int = 100) -> None:
+        """initTracers (index.html:1475-1483): from now on every step also moves,
+        culls and (every `interval` steps) injects tracers on the device."""
+        check("cfd_tracers_enable",
+              load().cfd_tracers_enable(self._hh(), int(capacity), int(interval)))
+        self._tracer_capacity = int(capacity)
+
+    def tracers_disable(self) -> None:
+        check("cfd_tracers_disable", load().cfd_tracers_disable(self._hh()))
+
+    def tracer_count(self) -> int:
+        n = C.c_uint64()
+        check("cfd_tracers_count", load().cfd_tracers_count(self._hh(), C.byref(n)))
+        return int(n.value)
+
+    def tracers(self):
+        """The tracer list in order: (x, y, initial_y), float64."""
+        n = self.tracer_count()
+        x, y, iy = (np.empty(n, np.float64) for _ in range(3))
+        got = C.c_uint64()
+        check("cfd_tracers_get", load().cfd_tracers_get(self._hh(), _dp(x), _dp(y), _dp(iy), n,
+                                                        C.byref(got)))
+        assert got.value == n
+        return x, y, iy
+
+    def set_tracers(self, x, y, initial_y) -> None:
+        x, y, iy = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+                    for a in (x, y, initial_y))
+        if not (x.size == y.size == iy.size):
+            raise ValueError("x, y and initial_y differ in length")
+        check("cfd_tracers_set", load().cfd_tracers_set(self._hh(), _dp(x), _dp(y), _dp(iy),
+                                                        x.size))
+
+    def tracers_advance(self, dt: float) -> None:
+        """One updateTracers(dt) (index.html:1485-1497) on the current u, v."""
+        check("cfd_tracers_advance", load().cfd_tracers_advance(self._hh(), float(dt)))
+
+    def tracers_inject(self) -> None:
+        check("cfd_tracers_inject", load().cfd_tracers_inject(self._hh()))
+
+    def tracer_density(self) -> np.ndarray:
+        """Tracers per pressure cell, (ny, nx) uint32, counted on the device."""
+        out = np.empty((self.grid.ny, self.grid.nx), np.uint32)
+        check("cfd_tracers_density", load().cfd_tracers_density(
+            self._hh(), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
     # ------------------------------------------------------------------ run
     def run(self) -> "SimulationControlHandle":
         """Model::run (model.rs:1282-1332): a worker thread owns the model and
@@ -616,6 +669,26 @@ class SimulationControlHandle:
         p = params._c()
         check("cfd_run_set_params", load().cfd_run_set_params(self._live(), C.byref(p)))
         self._model.params = params
+
+    def set_tracers(self, capacity: int, interval: int = 100):
+        """Enable tracers on the running model (capacity 0 disables): snapshots
+        published from then on carry the tracer list of the same step."""
+        check("cfd_run_set_tracers",
+              load().cfd_run_set_tracers(self._live(), int(capacity), int(interval)))
+        if capacity:
+            self._tracer_capacity = int(capacity)
+
+    def get_last_available_tracers(self):
+        """(x, y, initial_y) of the newest snapshot since the previous call, or None."""
+        cap = getattr(self, "_tracer_capacity", 0)
+        x, y, iy = (np.empty(cap, np.float64) for _ in range(3))
+        n, avail = C.c_uint64(), C.c_int()
+        check("cfd_run_last_tracers", load().cfd_run_last_tracers(
+            self._live(), _dp(x), _dp(y), _dp(iy), cap, C.byref(n), C.byref(avail)))
+        if not avail.value:
+            return None
+        k = int(n.value)
+        return x[:k].copy(), y[:k].copy(), iy[:k].copy()
 
     def pause(self):
         check("cfd_run_pause", load().cfd_run_pause(self._live()))

@@ -34,6 +34,9 @@ EXPORTS = [
     "cfd_mesh_from_quadtree", "cfd_mesh_sizes", "cfd_mesh_cells", "cfd_mesh_neighbors",
     "cfd_mesh_intersections", "cfd_mesh_full_bounding_box", "cfd_mesh_build_ms",
     "cfd_mesh_destroy",
+    "cfd_tracers_enable", "cfd_tracers_disable", "cfd_tracers_count", "cfd_tracers_get",
+    "cfd_tracers_set", "cfd_tracers_advance", "cfd_tracers_inject", "cfd_tracers_density",
+    "cfd_run_set_tracers", "cfd_run_last_tracers",
 ]
 
 
@@ -59,6 +62,7 @@ class CfdResiduals(C.Structure):
 
 
 FP = C.POINTER(C.c_float)
+DP = C.POINTER(C.c_double)
 
 
 class CfdState(C.Structure):
@@ -203,6 +207,18 @@ def load():
         "cfd_mesh_full_bounding_box": (i32, [vp, C.POINTER(CfdAabb)]),
         "cfd_mesh_build_ms": (i32, [vp, C.POINTER(C.c_double)]),
         "cfd_mesh_destroy": (None, [vp]),
+        # tracer particles
+        "cfd_tracers_enable": (i32, [vp, C.c_uint64, i32]),
+        "cfd_tracers_disable": (i32, [vp]),
+        "cfd_tracers_count": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "cfd_tracers_get": (i32, [vp, DP, DP, DP, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "cfd_tracers_set": (i32, [vp, DP, DP, DP, C.c_uint64]),
+        "cfd_tracers_advance": (i32, [vp, C.c_double]),
+        "cfd_tracers_inject": (i32, [vp]),
+        "cfd_tracers_density": (i32, [vp, C.POINTER(C.c_uint32)]),
+        "cfd_run_set_tracers": (i32, [vp, C.c_uint64, i32]),
+        "cfd_run_last_tracers": (i32, [vp, DP, DP, DP, C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get("CFD_LIB") and not hasattr(L, name):

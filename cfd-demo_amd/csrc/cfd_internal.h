@@ -382,6 +382,38 @@ void launch_abort_to_red(const Fields &f, hipStream_t s);
 // flag and host word (as the step finalize does)
 void launch_abort_from_red(const Fields &f, hipStream_t s);
 
+// ---- tracer particles (cfd_tracers.hip; index.html:1472-1543) ----
+// The script's ordered list {x, y, initialY} as three f64 arrays in two buffers
+// (the compaction writes the other one), with every word that decides a
+// launch on the device: a tracer step is the same two launches every step.
+constexpr int kTrcBlock = 256;   // workgroup = tile of the stable compaction
+struct TrcCtl {
+    uint32_t count;      // tracers in buffer `cur`
+    uint32_t overflow;   // sticky: an injection did not fit the capacity
+    uint32_t cur;        // buffer that holds the list
+    // written by the advect launch's last workgroup, read by the scatter
+    // launch (which writes count / cur: no launch reads a word it writes)
+    uint32_t n_prev, src, total, do_inject;
+    uint32_t ticket;     // workgroups of the advect launch that have finished
+};
+struct Tracers {
+    double *x0, *y0, *i0, *x1, *y1, *i1;   // buffers 0 and 1: x, y, initialY
+    TrcCtl *tc;
+    uint32_t *tile_cnt, *tile_off;   // survivors per tile of kTrcBlock, their exclusive scan
+    uint32_t cap;
+    uint32_t interval;    // inject when Ctl::step % interval == 0
+    double dx, dy, lx, ly;   // the model's f32 values widened, as the script's doubles
+};
+// One updateTracers on the current u, v and the compaction (two launches of
+// `grid` workgroups).  in_step: dt and the injection cadence come from Ctl
+// (after the step finalize); else dt is `dt` and nothing is injected.
+void launch_trc_step(const Geom &g, const Fields &f, const Tracers &t, int grid, bool in_step,
+                     double dt, hipStream_t s);
+// injectTracers: ny tracers appended in place (one workgroup), or the overflow word
+void launch_trc_inject(const Geom &g, const Tracers &t, hipStream_t s);
+// tracers per pressure cell into counts (nx*ny words, zeroed by the caller)
+void launch_trc_density(const Geom &g, const Tracers &t, int grid, uint32_t *counts, hipStream_t s);
+
 // Jacobi kernel geometry (exported for the roofline bookkeeping in bench).
 constexpr int kJacRowsPerWave = 16;
 constexpr int kMaxTemporal = 8;     // most sweeps per temporally blocked launch (kind 1: 4)

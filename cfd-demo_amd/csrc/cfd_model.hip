@@ -1818,6 +1818,9 @@ struct cfd_model {
         rc = allreduce_max_u32(f.ctl->red, 7);   // maxima, non-finite flag, solve residual, abort
         if (rc) return rc;
         launch_step_finalize(g, f, stream);
+        // updateTracers(dt) with the dt and step count the finalize has just
+        // written, then the injection (index.html:1231-1238)
+        if (trc_pool) launch_trc_step(g, f, trc, trc_grid, true, 0.0, stream);
         HIP_TRY(hipGetLastError());
         if (rec_step) HIP_TRY(hipEventRecord(ev_step1, stream));
         if (timing) timed_steps++;
@@ -1843,7 +1846,7 @@ struct cfd_model {
         return e && atoi(e) != 0;
     }();
     bool graph_ok() const {
-        return graph_enabled && !sharded() && !timing &&
+        return graph_enabled && !sharded() && !timing && !trc_pool &&
                params.pressure_solver == CFD_SOLVER_JACOBI;
     }
     void drop_graph() {
@@ -2053,6 +2056,38 @@ struct cfd_model {
         return 0;
     }
 
+    // ---- tracer particles (cfd_tracers.hip; cfd_tracers_* below) ---------
+    // One allocation: TrcCtl and the tile words, then x, y, initialY of both
+    // buffers.  While enabled it is one more segment of the self-recovery
+    // checkpoint (a replayed step moves the tracers again), and steps are not
+    // replayed from a captured graph (graph_ok).
+    Tracers trc{};
+    char *trc_pool = nullptr;
+    size_t trc_bytes = 0;
+    int trc_grid = 0;            // workgroups per launch: from the capacity, at most 8 per CU
+    uint32_t *trc_dens = nullptr;   // cfd_tracers_density's nx * ny counts
+    // the checkpoint pool is sized for its segments when ck_begin allocates it:
+    // whoever changes ck_segs (after a sync(): no checkpoint is open) drops it
+    int ck_drop_pool() {
+        if (ck_pool) HIP_TRY(hipFree(ck_pool));
+        ck_pool = nullptr;
+        ck_bytes = 0;
+        return 0;
+    }
+    int trc_release() {
+        if (!trc_pool) return 0;
+        for (size_t k = 0; k < ck_segs.size(); ++k)
+            if (ck_segs[k].ptr == (void *)trc_pool) {
+                ck_segs.erase(ck_segs.begin() + (long)k);
+                break;
+            }
+        if (int rc = ck_drop_pool()) return rc;
+        HIP_TRY(hipFree(trc_pool));
+        trc_pool = nullptr;
+        trc = Tracers{};
+        return 0;
+    }
+
     int read_ctl(Ctl *out) {
         int rc = sync();
         if (rc) return rc;
@@ -2084,6 +2119,8 @@ struct cfd_model {
             if (ptr) (void)hipFree(ptr);
         if (h_nonfinite) (void)hipHostFree(h_nonfinite);
         if (ck_pool) (void)hipFree(ck_pool);
+        if (trc_pool) (void)hipFree(trc_pool);
+        if (trc_dens) (void)hipFree(trc_dens);
         drop_graph();
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         if (ev_step0) (void)hipEventDestroy(ev_step0);
@@ -3002,6 +3039,168 @@ int cfd_set_state(cfd_model *m, const cfd_state *st) {
     rc = m->exchange_pp(c.cur, m->g.hg);
     if (rc) return rc;
     return m->sync();
+}
+
+// ---- tracer particles (index.html:1472-1543; kernels in cfd_tracers.hip) ----
+namespace {
+
+constexpr uint64_t kTrcMaxCap = 1ull << 30;
+
+const char *const kTrcOverflowMsg =
+    "tracer capacity overflow: an injection of ny tracers did not fit; the list is no longer the "
+    "script's until cfd_tracers_enable or cfd_tracers_set";
+
+// Drain the stream and fetch the tracer words; the sticky overflow is an error
+// of every reading call.
+int trc_read(cfd_model *m, TrcCtl *tc) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!m->trc_pool) return fail(CFD_ESTATE, "tracers are not enabled (cfd_tracers_enable)");
+    int rc = m->sync();
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(tc, m->trc.tc, sizeof(TrcCtl), hipMemcpyDeviceToHost));
+    if (tc->overflow) return fail(CFD_ESTATE, kTrcOverflowMsg);
+    return 0;
+}
+
+// The explicit calls change tracer state outside a step: they drain the stream
+// first, which commits the self-recovery checkpoint, so the next step takes a
+// fresh one that holds their result (no replay runs them twice).
+int trc_begin_call(cfd_model *m) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!m->trc_pool) return fail(CFD_ESTATE, "tracers are not enabled (cfd_tracers_enable)");
+    return m->sync();
+}
+
+}  // namespace
+
+int cfd_tracers_enable(cfd_model *m, uint64_t capacity, int inject_interval) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (m->sharded())
+        return fail(CFD_EINVAL, "tracers run on one domain only: a tracer reads u and v rows of "
+                                "other slabs");
+    const uint64_t ny = (uint64_t)m->g.ny;
+    if (capacity < ny || capacity > kTrcMaxCap)
+        return fail(CFD_EINVAL, "tracer capacity must be in [ny, 2^30] (ny = " + std::to_string(ny) + ")");
+    int rc = m->sync();
+    if (rc) return rc;
+    if ((rc = m->trc_release())) return rc;
+    m->drop_graph();
+    const size_t ntiles = (size_t)((capacity + kTrcBlock - 1) / kTrcBlock);
+    const size_t head = (256 + 2 * ntiles * 4 + 255) & ~(size_t)255;
+    const size_t arr = ((size_t)capacity * 8 + 255) & ~(size_t)255;
+    const size_t bytes = head + 6 * arr;
+    char *pool = nullptr;
+    HIP_TRY(hipMalloc((void **)&pool, bytes));
+    m->trc_pool = pool;
+    m->trc_bytes = bytes;
+    HIP_TRY(hipMemset(pool, 0, bytes));
+    Tracers &t = m->trc;
+    t.tc = (TrcCtl *)pool;
+    t.tile_cnt = (uint32_t *)(pool + 256);
+    t.tile_off = t.tile_cnt + ntiles;
+    double **arrs[6] = {&t.x0, &t.y0, &t.i0, &t.x1, &t.y1, &t.i1};
+    for (int k = 0; k < 6; ++k) *arrs[k] = (double *)(pool + head + (size_t)k * arr);
+    t.cap = (uint32_t)capacity;
+    t.interval = inject_interval <= 0 ? 100u : (uint32_t)inject_interval;   // tracerInjectionInterval :1534
+    t.dx = (double)m->g.dx;
+    t.dy = (double)m->g.dy;
+    t.lx = (double)m->grid.lx;
+    t.ly = (double)m->grid.ly;
+    // grid from the capacity; CFD_TRACER_WGS=N caps it (any N >= 1 gives the same bits)
+    long grid = std::min<long>((long)ntiles, 8l * std::max(1, m->g.n_cu));
+    if (const char *e = getenv("CFD_TRACER_WGS"))
+        if (atol(e) >= 1) grid = std::min<long>(grid, atol(e));
+    m->trc_grid = (int)std::max(1l, grid);
+    if ((rc = m->ck_drop_pool())) return rc;
+    m->ck_segs.push_back({pool, bytes});
+    launch_trc_inject(m->g, t, m->stream);   // initTracers (:1475-1483): the list was empty
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+int cfd_tracers_disable(cfd_model *m) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!m->trc_pool) return 0;
+    int rc = m->sync();
+    if (rc) return rc;
+    return m->trc_release();
+}
+
+int cfd_tracers_count(cfd_model *m, uint64_t *n) {
+    TrcCtl tc;
+    int rc = trc_read(m, &tc);
+    if (rc) return rc;
+    if (n) *n = tc.count;
+    return 0;
+}
+
+int cfd_tracers_get(cfd_model *m, double *x, double *y, double *initial_y, uint64_t max,
+                    uint64_t *n_out) {
+    TrcCtl tc;
+    int rc = trc_read(m, &tc);
+    if (rc) return rc;
+    const Tracers &t = m->trc;
+    const size_t n = (size_t)std::min<uint64_t>(tc.count, max);
+    if (x && n) HIP_TRY(hipMemcpy(x, tc.cur ? t.x1 : t.x0, n * 8, hipMemcpyDeviceToHost));
+    if (y && n) HIP_TRY(hipMemcpy(y, tc.cur ? t.y1 : t.y0, n * 8, hipMemcpyDeviceToHost));
+    if (initial_y && n) HIP_TRY(hipMemcpy(initial_y, tc.cur ? t.i1 : t.i0, n * 8, hipMemcpyDeviceToHost));
+    if (n_out) *n_out = n;
+    return 0;
+}
+
+int cfd_tracers_set(cfd_model *m, const double *x, const double *y, const double *initial_y,
+                    uint64_t n) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!m->trc_pool) return fail(CFD_ESTATE, "tracers are not enabled (cfd_tracers_enable)");
+    if (n > m->trc.cap) return fail(CFD_EINVAL, "more tracers than the capacity");
+    if (n && (!x || !y || !initial_y)) return fail(CFD_EINVAL, "null tracer array");
+    for (uint64_t k = 0; k < n; ++k)
+        if (!std::isfinite(x[k]) || !std::isfinite(y[k]) || !std::isfinite(initial_y[k]))
+            return fail(CFD_EINVAL, "non-finite tracer coordinate at index " + std::to_string(k));
+    int rc = m->sync();
+    if (rc) return rc;
+    const Tracers &t = m->trc;
+    if (n) {
+        HIP_TRY(hipMemcpy(t.x0, x, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t.y0, y, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t.i0, initial_y, (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    TrcCtl tc{};
+    tc.count = (uint32_t)n;   // buffer 0, no overflow, ticket 0
+    HIP_TRY(hipMemcpy(t.tc, &tc, sizeof(TrcCtl), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int cfd_tracers_advance(cfd_model *m, double dt) {
+    int rc = trc_begin_call(m);
+    if (rc) return rc;
+    launch_trc_step(m->g, m->f, m->trc, m->trc_grid, false, dt, m->stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int cfd_tracers_inject(cfd_model *m) {
+    int rc = trc_begin_call(m);
+    if (rc) return rc;
+    launch_trc_inject(m->g, m->trc, m->stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny) {
+    TrcCtl tc;
+    int rc = trc_read(m, &tc);
+    if (rc) return rc;
+    if (!counts_nx_ny) return fail(CFD_EINVAL, "null counts");
+    const size_t cells = (size_t)m->g.nx * (size_t)m->g.ny;
+    if (!m->trc_dens) HIP_TRY(hipMalloc((void **)&m->trc_dens, cells * 4));
+    HIP_TRY(hipMemsetAsync(m->trc_dens, 0, cells * 4, m->stream));
+    launch_trc_density(m->g, m->trc, m->trc_grid, m->trc_dens, m->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(counts_nx_ny, m->trc_dens, cells * 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return 0;
 }
 
 int cfd_get_masks(cfd_model *m, uint8_t *mask_u, uint8_t *mask_v) {

@@ -1,7 +1,8 @@
 // cfd_runtime.cpp — Model::run (/root/reference/src/model.rs:1282-1332) as a
 // native host runtime over the C ABI: a worker thread owns the model and, per
 // loop iteration, drains the command queue (Stop, SetParams, GetSnapshot,
-// Pause, Resume — model.rs:57-63, 1291-1315) and then either steps the model
+// Pause, Resume — model.rs:57-63, 1291-1315; SetTracers is this build's, for
+// the script's tracer checkbox, index.html:1306-1312) and then either steps the model
 // and publishes its residuals (:1317-1320) or sleeps 16 ms while paused
 // (:1322).  The mpsc channels of the reference become a mutex-guarded command
 // deque, a latest-snapshot slot (get_last_available_snapshot drains the
@@ -17,6 +18,7 @@
 // command loop (model.rs:1296) and its thread ends when a send fails after the
 // handle is dropped (:1304, :1319); here Stop ends the worker, and
 // cfd_run_stop joins it and hands the model back to the caller.
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -30,14 +32,26 @@
 
 extern "C" void cfdrt_set_error(const char *msg);   // cfd_model.hip (internal)
 extern "C" int cfdrt_check_params(const cfd_model *m, const cfd_params *p);   // ditto
+// The tracer entry points are bound weakly: this file also links against
+// partial implementations of the C ABI (the host sanitizer harness's stub
+// model has no tracers), where SetTracers then fails with CFD_ESTATE.
+extern "C" {
+__attribute__((weak)) int cfd_tracers_enable(cfd_model *m, uint64_t capacity, int inject_interval);
+__attribute__((weak)) int cfd_tracers_disable(cfd_model *m);
+__attribute__((weak)) int cfd_tracers_count(cfd_model *m, uint64_t *n);
+__attribute__((weak)) int cfd_tracers_get(cfd_model *m, double *x, double *y, double *initial_y,
+                                          uint64_t max, uint64_t *n_out);
+}
 
 namespace {
 
-enum CmdKind { CMD_STOP, CMD_PARAMS, CMD_SNAPSHOT, CMD_PAUSE, CMD_RESUME };
+enum CmdKind { CMD_STOP, CMD_PARAMS, CMD_SNAPSHOT, CMD_PAUSE, CMD_RESUME, CMD_TRACERS };
 
 struct Cmd {
     CmdKind kind;
     cfd_params params;
+    uint64_t trc_capacity = 0;   // CMD_TRACERS: 0 disables
+    int trc_interval = 0;
 };
 
 constexpr size_t kMaxQueuedResiduals = size_t(1) << 20;   // oldest dropped beyond this
@@ -57,6 +71,9 @@ struct cfd_runner {
     float snap_dt = 0.f;
     int snap_paused = 0;
     bool snap_ready = false;
+    // the tracer list of the newest snapshot taken with tracers enabled
+    std::vector<double> trc_x, trc_y, trc_i;
+    bool trc_ready = false;
     int status = 0;            // first failing cfd_* status of the worker
     std::string error;
     uint64_t steps = 0;
@@ -65,8 +82,9 @@ struct cfd_runner {
 };
 
 void cfd_runner::run() {
-    bool paused = false;
+    bool paused = false, tracers = false;
     std::vector<float> u(n_u), v(n_v), p(n_p);
+    std::vector<double> tx, ty, ti;
     for (;;) {
         std::deque<Cmd> batch;
         {
@@ -85,8 +103,22 @@ void cfd_runner::run() {
             } else if (c.kind == CMD_SNAPSHOT && !snapshot_sent) {
                 float dt = 0.f;
                 rc = cfd_get_snapshot(model, u.data(), v.data(), p.data(), &dt);
+                uint64_t nt = 0;
+                if (!rc && tracers) rc = cfd_tracers_count(model, &nt);
+                if (!rc && tracers) {
+                    tx.resize(nt);
+                    ty.resize(nt);
+                    ti.resize(nt);
+                    rc = cfd_tracers_get(model, tx.data(), ty.data(), ti.data(), nt, &nt);
+                }
                 if (!rc) {
                     std::lock_guard<std::mutex> lk(mu);
+                    if (tracers) {
+                        trc_x.swap(tx);
+                        trc_y.swap(ty);
+                        trc_i.swap(ti);
+                        trc_ready = true;
+                    }
                     snap_u.swap(u);
                     snap_v.swap(v);
                     snap_p.swap(p);
@@ -100,6 +132,14 @@ void cfd_runner::run() {
                     snap_ready = true;
                 }
                 snapshot_sent = true;
+            } else if (c.kind == CMD_TRACERS && !(cfd_tracers_enable && cfd_tracers_disable &&
+                                                  cfd_tracers_count && cfd_tracers_get)) {
+                cfdrt_set_error("this build of the model has no tracer entry points");
+                rc = CFD_ESTATE;
+            } else if (c.kind == CMD_TRACERS) {
+                rc = c.trc_capacity ? cfd_tracers_enable(model, c.trc_capacity, c.trc_interval)
+                                    : cfd_tracers_disable(model);
+                if (!rc) tracers = c.trc_capacity != 0;
             } else if (c.kind == CMD_PAUSE) {
                 paused = true;
             } else if (c.kind == CMD_RESUME) {
@@ -238,6 +278,29 @@ int cfd_run_last_snapshot(cfd_runner *r, float *u, float *v, float *p, float *dt
     if (dt_out) *dt_out = r->snap_dt;
     if (paused_out) *paused_out = r->snap_paused;
     r->snap_ready = false;
+    return 0;
+}
+
+int cfd_run_set_tracers(cfd_runner *r, uint64_t capacity, int inject_interval) {
+    Cmd c{};
+    c.kind = CMD_TRACERS;
+    c.trc_capacity = capacity;
+    c.trc_interval = inject_interval;
+    return post(r, c);
+}
+
+int cfd_run_last_tracers(cfd_runner *r, double *x, double *y, double *initial_y, uint64_t max,
+                         uint64_t *n_out, int *available) {
+    if (!r || !available) return run_fail(CFD_EINVAL, "null runner or available");
+    std::lock_guard<std::mutex> lk(r->mu);
+    *available = r->trc_ready ? 1 : 0;
+    if (!r->trc_ready) return 0;
+    const size_t n = (size_t)std::min<uint64_t>(r->trc_x.size(), max);
+    if (x && n) std::memcpy(x, r->trc_x.data(), n * 8);
+    if (y && n) std::memcpy(y, r->trc_y.data(), n * 8);
+    if (initial_y && n) std::memcpy(initial_y, r->trc_i.data(), n * 8);
+    if (n_out) *n_out = n;
+    r->trc_ready = false;
     return 0;
 }
 

@@ -361,6 +361,59 @@ int cfd_render(cfd_model *m, int mode, uint8_t *rgba, float *min_max_out);
 /* The mode's derived scalar field itself (nx*ny f32; slab rows when sharded). */
 int cfd_derive_field(cfd_model *m, int mode, float *out, float *min_max_out);
 
+/* ---- tracer particles (index.html:1472-1543), the script's fourth
+ * visualisation mode, as a device-side pass over the solver state ----
+ * A tracer is {x, y, initialY}; the list is ordered and the order is kept.
+ * All arithmetic is the script's, in double, on the model's f32 u, v, dx, dy,
+ * lx, ly and dt widened to double; the lists are the script's bit for bit
+ * (tests/golden/js_tracers_*.npz hold the script's own results under node).
+ * While enabled, every step of cfd_update / cfd_update_n ends as
+ * simulationLoop does (:1231-1238): updateTracers(dt) with the dt the step has
+ * just computed, then injectTracers() iff simulation_step % interval == 0 (the
+ * count after the step's increment) -- two launches, nothing read back, so a
+ * batch of n steps gives the same tracers as n single calls.  Disabled, a step
+ * enqueues nothing for them.  Tracers leaving [0, lx] x [0, ly] (or turning
+ * NaN) are dropped by a stable compaction; -0 and exactly lx stay.
+ * An injection that does not fit the capacity appends nothing and sets a
+ * sticky overflow word: cfd_tracers_count / _get / _density then return
+ * CFD_ESTATE until cfd_tracers_enable or cfd_tracers_set.
+ * One domain only: a tracer reads u and v rows of other slabs, so
+ * cfd_tracers_enable returns CFD_EINVAL on a sharded model (like
+ * CFD_SOLVER_SOR_LEX).  cfd_get_state / cfd_set_state do not touch tracers;
+ * cfd_tracers_get / cfd_tracers_set are their checkpoint.  The model's
+ * CFD_ETIMEOUT self-recovery covers them: the tracer buffers are part of its
+ * checkpoint, and the explicit calls below synchronise first, so the next
+ * checkpoint is taken after them.  Steps are not replayed from a captured
+ * graph (CFD_GRAPH=1) while tracers are enabled. */
+/* initTracers (:1475-1483): ny tracers at x = 0, y = (j + 0.5) dy.  capacity in
+ * [ny, 2^30]; inject_interval <= 0 means tracerInjectionInterval, 100 (:1534).
+ * Enabling again starts over. */
+int cfd_tracers_enable(cfd_model *m, uint64_t capacity, int inject_interval);
+/* tracers = [] (:1311); frees the buffers. */
+int cfd_tracers_disable(cfd_model *m);
+/* tracers.length.  Synchronises. */
+int cfd_tracers_count(cfd_model *m, uint64_t *n);
+/* The first min(count, max) tracers in list order (NULL skips an array);
+ * *n_out = tracers copied.  Synchronises. */
+int cfd_tracers_get(cfd_model *m, double *x, double *y, double *initial_y, uint64_t max,
+                    uint64_t *n_out);
+/* Replace the list.  CFD_EINVAL for n > capacity and for a non-finite value
+ * (the script would read u[NaN]); finite positions outside the domain are
+ * accepted: they take getVelocityAt's clamps (:1504-1507) and the next
+ * advance drops them.  Clears the overflow word. */
+int cfd_tracers_set(cfd_model *m, const double *x, const double *y, const double *initial_y,
+                    uint64_t n);
+/* One updateTracers(dt) (:1485-1497, getVelocityAt :1499-1525) on the current
+ * u, v; no injection.  Asynchronous. */
+int cfd_tracers_advance(cfd_model *m, double dt);
+/* One injectTracers() (:1537-1543).  Asynchronous. */
+int cfd_tracers_inject(cfd_model *m);
+/* Build-defined, in the spirit of cfd_render: tracers per pressure cell
+ * (nx*ny u32, row-major, x fastest), cell = floor(x/dx), floor(y/dy) clipped to
+ * the grid, so a large population need not cross PCIe to be drawn.  Integer
+ * atomics: exact and independent of order.  Synchronises. */
+int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny);
+
 /* The grid and parameters the model runs with (NULL skips either). */
 int cfd_get_config(const cfd_model *m, cfd_grid *grid, cfd_params *params);
 
@@ -389,6 +442,16 @@ int cfd_run_last_snapshot(cfd_runner *r, float *u, float *v, float *p, float *dt
 /* get_new_log_messages (:88-98): up to `max` queued residual records, oldest
  * first; *n_out = records copied. */
 int cfd_run_new_residuals(cfd_runner *r, cfd_residuals *out, int max, int *n_out);
+/* Command (drained in order with the others): cfd_tracers_enable(capacity,
+ * inject_interval) on the worker's model, or cfd_tracers_disable for capacity
+ * 0 (the script's checkbox, index.html:1306-1312).  While enabled, every
+ * snapshot the worker publishes carries the tracer list of the same step. */
+int cfd_run_set_tracers(cfd_runner *r, uint64_t capacity, int inject_interval);
+/* The tracers of the newest snapshot published since the previous call: the
+ * first min(count, max) in list order (NULL skips an array), *n_out = tracers
+ * copied; *available = 0 when there is none. */
+int cfd_run_last_tracers(cfd_runner *r, double *x, double *y, double *initial_y, uint64_t max,
+                         uint64_t *n_out, int *available);
 /* 0 while the worker is healthy, else the first failing status of a call it
  * made (it then stops stepping and waits for Stop); msg gets the message. */
 int cfd_run_status(cfd_runner *r, char *msg, size_t msg_len);
