@@ -31,7 +31,7 @@ __all__ = [
     "VelocityScheme", "InletProfile", "PressureSolver", "BoundaryKind", "Cylinder", "Grid",
     "SimulationParams", "Residuals", "SimSnapshot", "Model", "SimulationControlHandle",
     "CfdError", "default_grid", "cavity_grid", "rccl_unique_id", "device_count", "load", "LocalHub",
-    "VisualizationMode", "CFD_ENONFINITE",
+    "VisualizationMode", "CFD_ENONFINITE", "ScriptScheme", "ScriptPhase",
 ]
 
 
@@ -43,6 +43,17 @@ class VelocityScheme(enum.IntEnum):          # model.rs:141-146
 class InletProfile(enum.IntEnum):            # model.rs:154-159
     Uniform = 0
     Parabolic = 1
+
+
+class ScriptScheme(enum.IntEnum):            # index.html currentVelocityScheme (script_piso_step)
+    First = 0
+    Second = 1
+    Quick = 2
+
+
+class ScriptPhase(enum.IntEnum):             # the two passes of the script's pisoStep
+    Predict = 0                              # index.html:368-739
+    Correct = 1                              # :842-866, then applyBoundaryConditions
 
 
 class PressureSolver(enum.IntEnum):          # model.rs:148-152
@@ -283,6 +294,26 @@ class Model:
 
     def run_phase(self, phase: int, dt_sub: float) -> None:
         check("cfd_run_phase", load().cfd_run_phase(self._hh(), phase, dt_sub))
+
+    @staticmethod
+    def _script_step(dt_sub, scheme, inlet_velocity, inlet_profile):
+        from ._lib import CfdScriptStep
+        return CfdScriptStep(int(scheme), int(inlet_profile), float(inlet_velocity), float(dt_sub))
+
+    def script_piso_step(self, dt_sub: float, scheme, inlet_velocity: float,
+                         inlet_profile=InletProfile.Uniform) -> None:
+        """The script's own substep (index.html pisoStep(dt_sub) with
+        applyBoundaryConditions) in double over the f32 fields, `scheme` a
+        ScriptScheme (QUICK included); the solve in the middle is the model's
+        (pressure_solver Multigrid or SorLex only).  Asynchronous."""
+        s = self._script_step(dt_sub, scheme, inlet_velocity, inlet_profile)
+        check("cfd_script_piso_step", load().cfd_script_piso_step(self._hh(), C.byref(s)))
+
+    def script_phase(self, phase, dt_sub: float, scheme, inlet_velocity: float,
+                     inlet_profile=InletProfile.Uniform) -> None:
+        """One pass of script_piso_step alone (ScriptPhase), synchronous."""
+        s = self._script_step(dt_sub, scheme, inlet_velocity, inlet_profile)
+        check("cfd_script_phase", load().cfd_script_phase(self._hh(), int(phase), C.byref(s)))
 
     def synchronize(self) -> None:
         check("cfd_synchronize", load().cfd_synchronize(self._hh()))

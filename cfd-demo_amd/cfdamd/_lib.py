@@ -37,6 +37,7 @@ EXPORTS = [
     "cfd_tracers_enable", "cfd_tracers_disable", "cfd_tracers_count", "cfd_tracers_get",
     "cfd_tracers_set", "cfd_tracers_advance", "cfd_tracers_inject", "cfd_tracers_density",
     "cfd_run_set_tracers", "cfd_run_last_tracers",
+    "cfd_script_piso_step", "cfd_script_phase",
 ]
 
 
@@ -52,6 +53,11 @@ class CfdParams(C.Structure):
                 ("inlet_profile", C.c_int32), ("pressure_solver", C.c_int32),
                 ("jacobi_iters", C.c_int32), ("corrector_passes", C.c_int32),
                 ("tol_enabled", C.c_int32), ("p_tol", C.c_float), ("bc_kind", C.c_int32)]
+
+
+class CfdScriptStep(C.Structure):          # cfd_script_step
+    _fields_ = [("scheme", C.c_int32), ("inlet_profile", C.c_int32),
+                ("inlet_velocity", C.c_double), ("dt_sub", C.c_double)]
 
 
 class CfdResiduals(C.Structure):
@@ -208,6 +214,8 @@ def load():
         "cfd_mesh_build_ms": (i32, [vp, C.POINTER(C.c_double)]),
         "cfd_mesh_destroy": (None, [vp]),
         # tracer particles
+        "cfd_script_piso_step": (i32, [vp, C.POINTER(CfdScriptStep)]),
+        "cfd_script_phase": (i32, [vp, i32, C.POINTER(CfdScriptStep)]),
         "cfd_tracers_enable": (i32, [vp, C.c_uint64, i32]),
         "cfd_tracers_disable": (i32, [vp]),
         "cfd_tracers_count": (i32, [vp, C.POINTER(C.c_uint64)]),

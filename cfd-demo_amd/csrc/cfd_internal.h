@@ -414,6 +414,28 @@ void launch_trc_inject(const Geom &g, const Tracers &t, hipStream_t s);
 // tracers per pressure cell into counts (nx*ny words, zeroed by the caller)
 void launch_trc_density(const Geom &g, const Tracers &t, int grid, uint32_t *counts, hipStream_t s);
 
+// ---- the script's substep (cfd_script_step.hip; index.html:366-930) ----
+// The script's doubles as the model's f32 values widened, dx*dx and dy*dy as
+// the script forms them, and their reciprocals; fast = 1 when dx, dy, dx*dx
+// and dy*dy are all powers of two (x / c == x * (1/c) bit for bit).  obs_u /
+// obs_v: per row of u faces (ny rows) / v faces (ny+1 rows) the half-open
+// column interval [lo, hi) of isPointInObstacle at the face's own position
+// (0, 0: none); inlet: the ny values the boundary pass stores into u(0, j).
+struct ScriptStep {
+    double dx, dy, dxx, dyy, nu, dt;
+    double r_dx, r_dy, r_dxx, r_dyy;
+    const int32_t *obs_u, *obs_v;
+    const float *inlet;
+    int32_t fast;
+};
+// one domain, nx % 4 == 0, ny >= 4, u / v allocations under 2 GiB (buffer loads)
+bool script_step_ok(const Geom &g, const Fields &f);
+// u*, v*, rhs from u, v (:368-739) in one row march; scheme: CFD_SCRIPT_*
+void launch_script_predict(const Geom &g, const Fields &f, const ScriptStep &k, int scheme,
+                           hipStream_t s);
+// u, v from u*, v* and the current p', p += p', then the boundary pass (:842-866, :870-930)
+void launch_script_correct(const Geom &g, const Fields &f, const ScriptStep &k, hipStream_t s);
+
 // Jacobi kernel geometry (exported for the roofline bookkeeping in bench).
 constexpr int kJacRowsPerWave = 16;
 constexpr int kMaxTemporal = 8;     // most sweeps per temporally blocked launch (kind 1: 4)

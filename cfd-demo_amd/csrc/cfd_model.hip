@@ -2088,6 +2088,105 @@ struct cfd_model {
         return 0;
     }
 
+    // ---- the script's substep (cfd_script_step.hip; cfd_script_* below) ----
+    // One allocation, built at first use (the grid never changes after
+    // creation): the obstacle face intervals of u (2 ny ints) and v
+    // (2 (ny + 1) ints), then the ny inlet values, re-uploaded when a call's
+    // (inlet_velocity, profile) differs from the last upload's.
+    char *scr_pool = nullptr;
+    ScriptStep scr{};
+    std::vector<float> scr_inlet_h;
+    double scr_inlet_v = 0.0;
+    int scr_inlet_profile = -1;   // -1: nothing uploaded yet
+    // isPointInObstacle (:212-215) at one face position, in double
+    bool scr_in_obstacle(double x, double y) const {
+        if (!grid.has_cylinder) return false;
+        const double ex = x - (double)grid.cylinder_x, ey = y - (double)grid.cylinder_y;
+        return std::sqrt(ex * ex + ey * ey) <= (double)grid.cylinder_radius;
+    }
+    int script_build() {
+        if (scr_pool) return 0;
+        const int nx = g.nx, ny = g.ny;
+        const double dx = (double)g.dx, dy = (double)g.dy;
+        // every face is evaluated; a disc under correctly rounded monotone
+        // operations gives one interval per row, and that is checked, not assumed
+        std::vector<int32_t> iv((size_t)2 * ny + 2 * (ny + 1), 0);
+        auto row = [&](int32_t *out, int n, auto inside) -> bool {
+            int lo = -1, hi = -1, cnt = 0;
+            for (int i = 0; i < n; ++i)
+                if (inside(i)) {
+                    if (lo < 0) lo = i;
+                    hi = i + 1;
+                    ++cnt;
+                }
+            if (cnt && hi - lo != cnt) return false;
+            out[0] = cnt ? lo : 0;
+            out[1] = cnt ? hi : 0;
+            return true;
+        };
+        bool ok = true;
+        for (int j = 0; j < ny && ok; ++j)
+            ok = row(&iv[(size_t)2 * j], nx + 1,
+                     [&](int i) { return scr_in_obstacle((double)i * dx, ((double)j + 0.5) * dy); });
+        for (int j = 0; j <= ny && ok; ++j)
+            ok = row(&iv[(size_t)2 * ny + 2 * j], nx,
+                     [&](int i) { return scr_in_obstacle(((double)i + 0.5) * dx, (double)j * dy); });
+        if (!ok) return fail(CFD_ESTATE, "script step: a row's obstacle faces are not one interval");
+        const size_t ib = iv.size() * 4, bytes = ib + (size_t)ny * 4;
+        HIP_TRY(hipMalloc((void **)&scr_pool, bytes));
+        HIP_TRY(hipMemcpy(scr_pool, iv.data(), ib, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(scr_pool + ib, 0, (size_t)ny * 4));
+        scr.obs_u = (const int32_t *)scr_pool;
+        scr.obs_v = scr.obs_u + 2 * ny;
+        scr.inlet = (const float *)(scr_pool + ib);
+        scr.dx = dx;
+        scr.dy = dy;
+        scr.dxx = dx * dx;
+        scr.dyy = dy * dy;
+        scr.nu = (double)g.nu;
+        scr.r_dx = 1.0 / scr.dx;
+        scr.r_dy = 1.0 / scr.dy;
+        scr.r_dxx = 1.0 / scr.dxx;
+        scr.r_dyy = 1.0 / scr.dyy;
+        auto pow2 = [](double x) {
+            int e;
+            return std::frexp(x, &e) == 0.5;
+        };
+        scr.fast = pow2(scr.dx) && pow2(scr.dy) && pow2(scr.dxx) && pow2(scr.dyy) ? 1 : 0;
+        scr_inlet_h.assign((size_t)ny, 0.0f);
+        return 0;
+    }
+    // the call's ScriptStep: dt, viscosity (cfd_set_params may have changed
+    // it) and the inlet column (:873-885), uploaded in stream order
+    int script_prepare(const cfd_script_step *s, ScriptStep *out) {
+        if (int rc = script_build()) return rc;
+        scr.nu = (double)g.nu;
+        if (scr_inlet_profile != s->inlet_profile ||
+            std::memcmp(&scr_inlet_v, &s->inlet_velocity, 8) != 0) {
+            const int ny = g.ny;
+            const double ly = (double)grid.ly, dy = (double)g.dy;
+            for (int j = 0; j < ny; ++j) {
+                double val = s->inlet_velocity;
+                if (s->inlet_profile == CFD_INLET_PARABOLIC) {
+                    const double y = ((double)j + 0.5) * dy;
+                    const double center = ly / 2, radius = ly / 2;
+                    const double t = (y - center) / radius;
+                    val = s->inlet_velocity * (1 - t * t);   // Math.pow(t, 2) == t * t
+                    val = val > 0 ? val : (val != val ? val : 0.0);   // Math.max(val, 0)
+                }
+                scr_inlet_h[(size_t)j] = (float)val;
+            }
+            // pageable source: the copy has left scr_inlet_h when the call returns
+            HIP_TRY(hipMemcpyAsync((void *)scr.inlet, scr_inlet_h.data(), (size_t)ny * 4,
+                                   hipMemcpyHostToDevice, stream));
+            scr_inlet_v = s->inlet_velocity;
+            scr_inlet_profile = s->inlet_profile;
+        }
+        *out = scr;
+        out->dt = s->dt_sub;
+        return 0;
+    }
+
     int read_ctl(Ctl *out) {
         int rc = sync();
         if (rc) return rc;
@@ -2121,6 +2220,7 @@ struct cfd_model {
         if (ck_pool) (void)hipFree(ck_pool);
         if (trc_pool) (void)hipFree(trc_pool);
         if (trc_dens) (void)hipFree(trc_dens);
+        if (scr_pool) (void)hipFree(scr_pool);
         drop_graph();
         for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
         if (ev_step0) (void)hipEventDestroy(ev_step0);
@@ -3201,6 +3301,70 @@ int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny) {
     HIP_TRY(hipMemcpyAsync(counts_nx_ny, m->trc_dens, cells * 4, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
     return 0;
+}
+
+// ---- the script's substep (index.html:366-930; kernels in cfd_script_step.hip) ----
+namespace {
+
+int script_check(cfd_model *m, const cfd_script_step *s) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!s) return fail(CFD_EINVAL, "null cfd_script_step");
+    if (m->sharded())
+        return fail(CFD_EINVAL, "the script substep runs on one domain only");
+    if (m->params.bc_kind != CFD_BC_CHANNEL)
+        return fail(CFD_EINVAL, "the script substep has the channel boundary conditions only");
+    if (m->params.pressure_solver != CFD_SOLVER_MULTIGRID &&
+        m->params.pressure_solver != CFD_SOLVER_SOR_LEX)
+        return fail(CFD_EINVAL, "the script substep needs pressure_solver 2 (multigrid) or 4 "
+                                "(script-order SOR): the others are not the script's");
+    if (s->scheme != CFD_SCRIPT_FIRST && s->scheme != CFD_SCRIPT_SECOND && s->scheme != CFD_SCRIPT_QUICK)
+        return fail(CFD_EINVAL, "script scheme must be 0 (first), 1 (second) or 2 (quick)");
+    if (s->inlet_profile != CFD_INLET_UNIFORM && s->inlet_profile != CFD_INLET_PARABOLIC)
+        return fail(CFD_EINVAL, "unknown inlet profile");
+    if (!std::isfinite(s->dt_sub) || !(s->dt_sub > 0.0))
+        return fail(CFD_EINVAL, "dt_sub must be finite and positive");
+    if (!std::isfinite(s->inlet_velocity)) return fail(CFD_EINVAL, "inlet_velocity must be finite");
+    if (!script_step_ok(m->g, m->f))
+        return fail(CFD_EINVAL, "grid too large for the script substep's row loads (2 GiB per field)");
+    return 0;
+}
+
+}  // namespace
+
+int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s) {
+    if (int rc = script_check(m, s)) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->invalidate_sums()) return rc;
+    if (int rc = m->ck_begin()) return rc;
+    const cfd_script_step st = *s;
+    auto run = [m, st]() {
+        ScriptStep k;
+        if (int rc = m->script_prepare(&st, &k)) return rc;
+        launch_script_predict(m->g, m->f, k, st.scheme, m->stream);
+        HIP_TRY(hipGetLastError());
+        if (int rc = m->enqueue_solve(-1)) return rc;
+        launch_script_correct(m->g, m->f, k, m->stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    m->ck_record(run);
+    return run();
+}
+
+int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s) {
+    if (int rc = script_check(m, s)) return rc;
+    if (phase != CFD_SCRIPT_PHASE_PREDICT && phase != CFD_SCRIPT_PHASE_CORRECT)
+        return fail(CFD_EINVAL, "unknown script phase");
+    HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->invalidate_sums()) return rc;
+    ScriptStep k;
+    if (int rc = m->script_prepare(s, &k)) return rc;
+    if (phase == CFD_SCRIPT_PHASE_PREDICT)
+        launch_script_predict(m->g, m->f, k, s->scheme, m->stream);
+    else
+        launch_script_correct(m->g, m->f, k, m->stream);
+    HIP_TRY(hipGetLastError());
+    return m->sync();
 }
 
 int cfd_get_masks(cfd_model *m, uint8_t *mask_u, uint8_t *mask_v) {

@@ -414,6 +414,55 @@ int cfd_tracers_inject(cfd_model *m);
  * atomics: exact and independent of order.  Synchronises. */
 int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny);
 
+/* ---- the script's own substep (index.html:366-867 pisoStep with
+ * :870-930 applyBoundaryConditions) ----
+ * What SURVEY Appendix B lists as the JavaScript variant's differences from
+ * model.rs, on the device: the u flux through an averaged v, the obstacle
+ * tested at each face's own position (isPointInObstacle, `<=` included) rather
+ * than through the cell masks of cfd_get_masks, no re-correction loop, double
+ * arithmetic over f32 arrays, and the third advection scheme, QUICK.  All
+ * arithmetic is the script's, in double, on the model's f32 u, v, p, p', dx, dy,
+ * lx, ly and viscosity widened (the convention of cfd_tracers_*); each value
+ * stored into a field is rounded to f32 once, as a Float32Array store is.  The
+ * fields are the script's bit for bit (tests/golden/js_step_*.npz hold the
+ * script's own results under node).  Nothing of the script is "fixed": faces
+ * its loops do not visit keep u / v; the second-order and QUICK y-Laplacian of
+ * v is (v[idx+2] - 2 v[idx] + v[idx]) / dy^2; every index guard is as written;
+ * rhs = (du/dx + dv/dy) / dt_sub over all cells; p += p' over all cells; the
+ * boundary pass runs in the script's order (inlet, outlet copy, rows 0 and
+ * ny-1 of u, rows 0 and ny of v, obstacle faces).
+ * The solve between the two passes is the model's own, unchanged, and must be
+ * one of the two pinned to the script: pressure_solver CFD_SOLVER_MULTIGRID or
+ * CFD_SOLVER_SOR_LEX (both restart p' from 0); any other returns CFD_EINVAL
+ * (the script's omega 0.7 Jacobi is not implemented; the red-black SOR and the
+ * Rust Jacobi are not the script's).  Its settings come from cfd_params (the
+ * script's own: jacobi_iters 50, tol_enabled 1, p_tol 1e-4); its residual lands
+ * in cfd_get_state().last_p_residual and jacobi_sweeps_total grows as the solve
+ * makes it grow.  simulation_step, dt and the u / v residuals are not touched:
+ * like cfd_piso_step this is the substep, not updateSimulation (the caller
+ * owns the inlet ramp of :277-281, dt / substepCount and the extrapolation).
+ * CFD_EINVAL also for a sharded model (one domain only, as CFD_SOLVER_SOR_LEX
+ * and tracers), bc_kind CFD_BC_CAVITY (the script has the channel only), an
+ * unknown scheme or profile, a non-finite or non-positive dt_sub and a
+ * non-finite inlet_velocity.  velocity_scheme in cfd_params still takes 0 or 1
+ * only, and cfd_update never takes this path.  The obstacle faces (per row of
+ * faces one column interval; has_cylinder == 0: none) and the inlet column are
+ * evaluated on the host in double (sqrt, the parabola) and uploaded. */
+enum { CFD_SCRIPT_FIRST = 0, CFD_SCRIPT_SECOND = 1, CFD_SCRIPT_QUICK = 2 };
+typedef struct {
+    int32_t scheme;          /* currentVelocityScheme: "first" / "second" / "quick" */
+    int32_t inlet_profile;   /* CFD_INLET_UNIFORM / CFD_INLET_PARABOLIC (inletProfileSelect) */
+    double  inlet_velocity;  /* currentInletVelocity (the caller owns the script's ramp, :277-281) */
+    double  dt_sub;          /* dt / substepCount (:282) */
+} cfd_script_step;
+/* pisoStep(dt_sub) + applyBoundaryConditions(), asynchronous like cfd_piso_step:
+ * two launches (k_script_predict, k_script_correct) around the solve's. */
+int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s);
+/* Its two passes alone, synchronous, for known-answer tests. */
+enum { CFD_SCRIPT_PHASE_PREDICT = 0,   /* :368-739  u*, v*, rhs             */
+       CFD_SCRIPT_PHASE_CORRECT = 1 }; /* :842-866  u, v, p += p', then BCs */
+int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s);
+
 /* The grid and parameters the model runs with (NULL skips either). */
 int cfd_get_config(const cfd_model *m, cfd_grid *grid, cfd_params *params);
 
