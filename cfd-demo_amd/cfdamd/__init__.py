@@ -537,6 +537,16 @@ class Model:
         return int(n.value)
 
     @property
+    def resident_geometry(self) -> dict:
+        """Tile plan of the resident solve (cfd_get_resident_geometry): rows
+        (br) and columns (bc) of a tile, tiles in the grid, workgroups launched;
+        CfdError CFD_ESTATE where the model does not take the resident solve."""
+        v = [C.c_int32() for _ in range(4)]
+        check("cfd_get_resident_geometry",
+              load().cfd_get_resident_geometry(self._hh(), *(C.byref(x) for x in v)))
+        return dict(br=v[0].value, bc=v[1].value, tiles=v[2].value, wgs=v[3].value)
+
+    @property
     def persist_blocks(self) -> int:
         """8-sweep blocks the last fixed-count solve ran in one persistent
         launch (k_jacobi_persist); 0 when every block had its own launch."""

@@ -137,7 +137,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_jacobi_resident(
                          bool publish) {
         for (int t = wg; t < ntiles; t += G) {
             const int ty = t / tiles_x, tx = t - ty * tiles_x;
-            const int r0 = ty * BR, r1 = min(ny, r0 + BR);
+            // A last tile row of the single row ny-1 (ny % BR == 1) would hold
+            // no interior row, and row ny-1 is a copy of the same sweep's row
+            // ny-2: that tile starts at row ny-2 (min), so the row it copies is
+            // computed in its every sweep.  It then overlaps the tile above by
+            // that row: both compute, fold into the residual maximum and
+            // store the same bits for it.
+            const int r0 = min(ty * BR, ny - 2), r1 = min(ny, r0 + BR);
             const int c0 = tx * BC, c1 = min(nx, c0 + BC);
             const int R0 = max(0, r0 - T), R1 = min(ny, r1 + T);
             const int C0 = max(0, c0 - T), C1 = min(nx, c1 + T);

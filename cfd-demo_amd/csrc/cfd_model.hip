@@ -3596,6 +3596,18 @@ int cfd_get_resident_solves(const cfd_model *m, uint64_t *solves) {
     return 0;
 }
 
+int cfd_get_resident_geometry(const cfd_model *m, int *br, int *bc, int *tiles, int *wgs) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    int v[4] = {0, 0, 0, 0};
+    if (!m->resident_mode() || !jacobi_resident_geometry(m->g, &v[0], &v[1], &v[2], &v[3]))
+        return fail(CFD_ESTATE, "the model does not take the resident solve");
+    if (br) *br = v[0];
+    if (bc) *bc = v[1];
+    if (tiles) *tiles = v[2];
+    if (wgs) *wgs = v[3];
+    return 0;
+}
+
 int cfd_get_persist_blocks(const cfd_model *m, int *blocks) {
     if (!m || !blocks) return fail(CFD_EINVAL, "null argument");
     *blocks = m->last_persist_blocks;

@@ -312,6 +312,11 @@ int cfd_get_recoveries(const cfd_model *m, uint64_t *n);
 /* Tolerance-mode solves this model enqueued as one resident launch
  * (k_jacobi_resident, see cfd_get_jacobi_kernel kind 6); diagnostics. */
 int cfd_get_resident_solves(const cfd_model *m, uint64_t *solves);
+/* The tile plan of that resident launch as the model's next tolerance-mode
+ * solve would take it: rows and columns of a tile's output cells, tiles in the
+ * grid and workgroups launched.  CFD_ESTATE when the model would not take the
+ * resident solve (kind != 6).  Read-only; diagnostics. */
+int cfd_get_resident_geometry(const cfd_model *m, int *br, int *bc, int *tiles, int *wgs);
 /* The tile geometry of the model's 8-sweep kind-5 Jacobi launch over its
  * first block's rows (persist != 0: the persistent form's): the dynamic LDS
  * pad in bytes (24 KiB caps a CU at 3 four-wave workgroups on cache-resident

@@ -214,6 +214,186 @@ def spike_state(nx, ny, seed, col, row, nan_in=None):
     return pp, rhs
 
 
+# ---------------------------------------------------------------------------
+# the resident solve's seam tests (test_gpu_resident_seams.py on the device,
+# test_resident_seams_cpu.py for their premises with the oracle alone)
+
+RES_T = 10               # sweeps per block of k_jacobi_resident between grid barriers
+RES_LIMIT = 50           # jacobi_iters of the spike solves (the reference's default)
+RES_BR, RES_BC = 8, 48   # the tile every small shape takes (asserted on the device)
+# the small shapes: what each pins is listed in test_gpu_resident_seams.py
+RES_SHAPES = [(16, 4), (48, 8), (16, 9), (24, 9), (56, 9), (104, 16), (96, 17), (120, 37),
+              (16, 65), (16, 72), (16, 257)]
+# the 800-wide grid whose 8 x 48 tiling no longer fits 256 CUs: 19-row tiles,
+# 248 = 13 * 19 + 1 (asserted on the device through the geometry getter)
+RES_WIDE = (800, 248)
+RES_WIDE_BR, RES_WIDE_BC = 19, 46
+RES_ITERS = (1, 2, 3, 9, 10, 11, 19, 50)   # Tb 1, 2, 3, both sides of a block, a ragged last block
+RES_NAN_ITERS = 4
+# exit sweeps the loose tolerances of the signs / range solves are built for
+# (tol_exiting_at): the middle of the first block and of the second
+RES_MID_EXITS = (4, 14)
+
+# tolerances of the spike solves per (nx, ny, spacing): over the shape's spike
+# states the reference's early exit falls on every sweep 1..10, on at least
+# three sweeps of 11..49 and never (50 sweeps) -- exit_stages_missing(),
+# asserted in test_resident_seams_cpu.py.  1e-4 is the reference's default.
+RES_P_TOLS = {
+    (16, 4, "pow2"): (0.025, 0.008, 0.006, 0.0012, 1e-4),
+    (16, 4, "div"): (0.08, 0.02, 0.012, 0.006, 0.0015, 1e-4),
+    (48, 8, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (48, 8, "div"): (0.15, 0.09, 0.025, 0.01, 0.006, 1e-4),
+    (16, 9, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (16, 9, "div"): (0.12, 0.015, 0.012, 0.009, 0.006, 1e-4),
+    (24, 9, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (24, 9, "div"): (0.07, 0.008, 0.005, 1e-4),
+    (56, 9, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (56, 9, "div"): (0.15, 0.09, 0.025, 0.01, 0.006, 1e-4),
+    (104, 16, "pow2"): (0.08, 0.01, 0.006, 0.005, 1e-4),
+    (104, 16, "div"): (0.03, 0.01, 0.0012, 1e-4),
+    (96, 17, "pow2"): (0.08, 0.01, 0.006, 0.005, 1e-4),
+    (96, 17, "div"): (0.09, 0.025, 0.009, 0.0012, 1e-4),
+    (120, 37, "pow2"): (0.08, 0.01, 0.006, 0.005, 1e-4),
+    (120, 37, "div"): (0.1, 0.007, 1e-4, 6e-5),
+    (16, 65, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (16, 65, "div"): (0.015, 0.01, 0.0012, 1e-4),
+    (16, 72, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (16, 72, "div"): (0.015, 0.01, 0.001, 1e-4),
+    (16, 257, "pow2"): (0.09, 0.01, 0.006, 0.005, 1e-4),
+    (16, 257, "div"): (0.1, 0.015, 0.012, 0.0012, 1e-4, 3e-5),
+}
+# The wide grid is no exit-stage shape: a solve of its 198 K cells costs the
+# oracle what a hundred of the small shapes' do, so it takes four spike cells
+# (a corner of the first tile seams, the last swept row) and three tolerances
+# (an exit in the first block, in a later one, and the default)
+RES_WIDE_P_TOLS = (0.01, 0.002, 1e-4)
+RES_WIDE_SPIKES = ((45, 18), (46, 19), (1, 246), (798, 246))
+
+
+def resident_spike_columns(nx, bc=RES_BC):
+    """spike_columns() plus both sides of the first two seams between tile
+    columns (47, 48, 95, 96 for 48-column tiles), where the grid has them."""
+    seams = list(range(bc, nx, bc))[:2]
+    return sorted(set(spike_columns(nx)) | {c for s in seams for c in (s - 1, s) if c <= nx - 2})
+
+
+def resident_spike_rows(ny, br=RES_BR):
+    """First swept row, both sides of the first tile-row seam, and the last
+    two swept rows, where the grid has them."""
+    return sorted({r for r in (1, br - 1, br, ny - 3, ny - 2) if 1 <= r <= ny - 2})
+
+
+def jacobi_history(nx, ny, kind, pp, rhs, iters=RES_LIMIT):
+    """(fields, residuals) of the oracle's Jacobi sweep by sweep: fields[k] is
+    p' after k sweeps (fields[0] the input), residuals[k] the residual of
+    sweep k (residuals[0] is None).  One-sweep solves chained: a sweep reads
+    nothing but p' and rhs."""
+    from oracle import OracleModel
+    lx, ly = spacing(nx, ny, kind)
+    o = OracleModel(nx, ny, lx, ly, jacobi_iters=1, tol_enabled=0)
+    o.field("p_prime")[:] = pp
+    o.field("rhs")[:] = rhs
+    fields, res = [np.array(pp, np.float32)], [None]
+    for _ in range(iters):
+        res.append(np.float32(o.jacobi()))
+        fields.append(o.field("p_prime").copy())
+    return fields, res
+
+
+def exit_sweep(res, p_tol, iters=RES_LIMIT):
+    """Sweeps a tolerance-mode solve of at most `iters` runs (model.rs:816),
+    from jacobi_history's residuals."""
+    for k in range(1, iters + 1):
+        if res[k] < np.float32(p_tol):
+            return k
+    return iters
+
+
+def tol_exiting_at(res, k):
+    """A tolerance under which the solve exits at sweep k exactly: half-way
+    between residual k and the smallest residual before it (None where
+    residual k is not below all of them)."""
+    before = min(res[1:k])
+    if not res[k] < before:
+        return None
+    tol = np.float32(0.5 * (float(res[k]) + float(before)))
+    return float(tol) if res[k] < tol <= before else None
+
+
+def exit_stages_missing(exits, T=RES_T, limit=RES_LIMIT):
+    """What a set of exit sweeps lacks of: every sweep of the first block
+    (every j, j = T-1 with no re-run included), three stages of a later block,
+    and the limit.  Empty when complete."""
+    missing = [k for k in range(1, T + 1) if k not in exits]
+    if len([e for e in exits if T < e < limit]) < 3:
+        missing.append("three of %d..%d" % (T + 1, limit - 1))
+    if limit not in exits:
+        missing.append(limit)
+    return missing
+
+
+def stale_row_indistinct(fields, n, nx, ny):
+    """The earlier sweeps (of n-1, n-2) whose row ny-2 equals sweep n's in
+    every column 1..nx-2, bit for bit: a row ny-1 copied from such a sweep
+    could not be told from the right one.  Empty where a stale copy shows."""
+    def row(k):
+        return bits(fields[k].reshape(ny, nx)[ny - 2, 1:nx - 1])
+    return [k for k in (n - 1, n - 2) if k >= 0 and np.array_equal(row(k), row(n))]
+
+
+# whole steps with the tolerance on: (nx, ny, spacing, cylinder)
+RES_STEP_CASES = {
+    "24x9": (24, 9, "pow2", None),
+    "96x17": (96, 17, "pow2", None),
+    "16x65": (16, 65, "pow2", None),
+    "96x17-cylinder": (96, 17, "div", (7.5, 5.0, 0.75)),
+}
+
+
+# p_tol of the whole steps: the default, under which every solve of these
+# states runs its 50 sweeps and every pass runs, and a loose one under which
+# the corrector loop ends early within two steps (test_resident_seams_cpu.py)
+RES_STEP_LOOSE = {"24x9": 0.01, "96x17": 0.01, "16x65": 0.01, "96x17-cylinder": 0.03}
+
+
+def resident_step_case(name):
+    """(grid, params) of a whole-step case: the lid-driven cavity on the
+    power-of-two spacing, the channel with a cylinder on the 30 x 10 domain."""
+    nx, ny, kind, cyl = RES_STEP_CASES[name]
+    lx, ly = spacing(nx, ny, kind)
+    g = dict(nx=nx, ny=ny, lx=lx, ly=ly)
+    if cyl:
+        return dict(g, cylinder=cyl), dict()
+    return g, dict(bc_kind=1, viscosity=0.01)
+
+
+def seam_nan_cells(nx, ny, br=RES_BR, bc=RES_BC):
+    """(col, row) beside the first tile seams: rows br-1 and br at a middle
+    column, columns bc-1 and bc at a middle row, where the grid has the seam
+    and the cell is swept."""
+    out = []
+    if ny > br:
+        out +=[(min(nx // 2, nx - 2), r) for r in (br - 1, br) if r <= ny - 2]
+    if nx - 1 > bc:
+        out += [(c, min(max(ny // 2, 1), ny - 2)) for c in (bc - 1, bc)]
+    return out
+
+
+# planted-NaN shapes: every small shape with a tile seam whose spoilt share
+# stays under the suite's cap of 0.20 (test_resident_seams_cpu.py).  16 x 9 has
+# the seam but not the room: a NaN at (8, 7) reaches 34 of its 144 cells in 4
+# sweeps, so it has no NaN flavour.
+RES_NAN_SHAPES = [s for s in RES_SHAPES if seam_nan_cells(*s) and s != (16, 9)]
+
+
+def seam_nan_state(nx, ny, cell, nan_in):
+    """(p', rhs) of adversarial_state's `signs` with one NaN at cell (col, row)."""
+    st = adversarial_state(nx, ny, 1, "signs")
+    pp, rhs = st["p_prime"].copy(), st["rhs"].copy()
+    {"p_prime": pp, "rhs": rhs}[nan_in][cell[0] + cell[1] * nx] = np.nan
+    return pp, rhs
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

@@ -90,6 +90,18 @@ def test_invalid_arguments_rejected_before_device():
         assert e.value.code == -1
 
 
+def test_resident_geometry_getter_is_declared_and_rejects_null():
+    """cfd_get_resident_geometry (the resident solve's tile plan) is part of
+    the ABI and fails with CFD_EINVAL, not a crash, on a null model."""
+    from cfdamd import _lib
+    L = _lib.load()
+    assert "cfd_get_resident_geometry" in header_symbols()
+    assert "cfd_get_resident_geometry" in _lib.EXPORTS
+    v = [C.c_int32(7) for _ in range(4)]
+    assert L.cfd_get_resident_geometry(None, *(C.byref(x) for x in v)) == _lib.CFD_EINVAL
+    assert [x.value for x in v] == [7] * 4
+
+
 def test_solver_choice_validated_before_device():
     """pressure_solver 0..2 (all three run on slabs since r2:
     tests/test_gpu_sharded.py); anything else is rejected before the device."""
