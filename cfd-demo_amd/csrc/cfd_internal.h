@@ -1,6 +1,6 @@
 // cfd_internal.h — device-side data layout and kernel launch interface of the
 // MI355X pressure-projection path.  Shared by cfd_kernels.hip (device code)
-// and cfd_model.hip (host runtime behind include/cfd.h).
+// and cfd_model.h / cfd_model_*.hip (host runtime behind include/cfd.h).
 //
 // Layout in HBM (one slab per GPU; a single-GPU model is the 1-slab case):
 //   every field is row-major with x fastest and the reference's pitches
@@ -120,7 +120,7 @@ struct Geom {
     // Jacobi divisors exactly as model.rs:740-746 forms them, their rounded
     // reciprocals, and the division mode proven exact for all three
     // (0: IEEE `/`, 1: x * (1/c), 2: x * (1/c) + one FMA correction step);
-    // see verify_division() in cfd_model.hip.
+    // see choose_division() in cfd_model_build.hip.
     float dx_sq, dy_sq, denom;
     float r_dx_sq, r_dy_sq, r_denom;
     int32_t fastdiv;

@@ -42,7 +42,7 @@ MG_MARCH_ROWS = 128 - 15                      # :544  mg_march_rows<false>() wit
 MG_MARCH_ROWS_RES = 128 - 17                  # :544  mg_march_rows<true>(): 111
 SOR_PAIRS = 62                                # :244  c = wc * 62 - 1 + lane (launcher :796): 124 columns
 SOR_SEG_ROWS, SOR_SEG_ROWS_BIG = 16, 32       # :767  kSorRows, kSorRowsBig (chosen at :797)
-MG_TAIL_CELLS = 4096                          # :15-16 "default 64 x 64 cells" (mg_build, cfd_model.hip:701)
+MG_TAIL_CELLS = 4096                          # :15-16 "default 64 x 64 cells" (mg_build, cfd_model_solvers.hip)
 
 MAX_NONFINITE_SHARE = 0.20                    # as tests/test_gpu_adversarial.py
 
@@ -78,7 +78,7 @@ SOR_TOL_NY = (17, 18, 19, 33, 34, 35)         # the row categories, tolerance on
 # ------------------------------------------------------------- the shape table
 
 def mg_levels(nx, ny):
-    """mgVcycle's recursion (index.html:1444-1451; mg_build, cfd_model.hip:694-698)."""
+    """mgVcycle's recursion (index.html:1444-1451; mg_build, cfd_model_solvers.hip)."""
     dims = [(nx, ny)]
     while not (dims[-1][0] <= 4 or dims[-1][1] <= 4):
         dims.append(((dims[-1][0] + 1) // 2, (dims[-1][1] + 1) // 2))
@@ -87,7 +87,7 @@ def mg_levels(nx, ny):
 
 def mg_grid_wide(nx, ny, tail):
     """Levels above k_mg_tail: those before the first one of at most
-    CFD_MG_TAIL cells, the coarsest always inside (cfd_model.hip:700-708)."""
+    CFD_MG_TAIL cells, the coarsest always inside (mg_build, cfd_model_solvers.hip)."""
     dims = mg_levels(nx, ny)
     thr = MG_TAIL_CELLS if tail == "default" else int(tail)
     first = next((l for l, (a, b) in enumerate(dims) if a * b <= thr), len(dims) - 1)

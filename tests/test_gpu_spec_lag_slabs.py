@@ -7,7 +7,7 @@ test under -x):
   speculative launch checks the previous launch's residuals, the re-run
   checks the last launch's;
 * CFD_SPEC_SLABS=1 -- the tolerance mode on slabs as speculative T-sweep
-  blocks (enqueue_spec_slabs, cfd_model.hip) instead of the host-driven loop,
+  blocks (enqueue_spec_slabs, cfd_model_jacobi.hip) instead of the host-driven loop,
   stopping on the host's read of each block's all-reduced residuals (r6).
 Every case is bitwise against the oracle and against the other path.
 """

@@ -184,7 +184,7 @@ def _worker(rank, n, port, cases, results):
                     T, lo, hi, ex = plan_block(j0, nyl, ny, hg, it, t_max, iters)
                     split, ov = plan_overlap(nyl, hg, rank, n, lo, hi) if (ovl and ex) else (False, None)
                     if split:
-                        # the overlapped schedule of cfd_model.hip: bands the
+                        # the overlapped schedule of enqueue_jacobi_slabs (cfd_model_jacobi.hip): bands the
                         # exchange sends first, their exchange in flight while
                         # the interior is computed, then the wait
                         src, dst = bufs[cur], bufs[cur ^ 1]
@@ -331,7 +331,7 @@ def test_single_domain_blocks_split_evenly():
 
 # ---------------------------------------------------------------------------
 # r5: the tolerance mode on slabs as speculative T-sweep blocks
-# (enqueue_spec_slabs, cfd_model.hip; opt-in CFD_SPEC_SLABS=1).  The same
+# (enqueue_spec_slabs, cfd_model_jacobi.hip; opt-in CFD_SPEC_SLABS=1).  The same
 # schedule in numpy over gloo: per block ONE p' exchange T rows deep (the
 # first block's also carries the rhs ghosts, r6), T sweeps of the owned rows
 # (sweep s recomputing T-1-s ghost rows each side), ONE all-reduce of the
