@@ -31,7 +31,7 @@ __all__ = [
     "VelocityScheme", "InletProfile", "PressureSolver", "BoundaryKind", "Cylinder", "Grid",
     "SimulationParams", "Residuals", "SimSnapshot", "Model", "SimulationControlHandle",
     "CfdError", "default_grid", "cavity_grid", "rccl_unique_id", "device_count", "load", "LocalHub",
-    "VisualizationMode", "CFD_ENONFINITE", "ScriptScheme", "ScriptPhase",
+    "VisualizationMode", "CFD_ENONFINITE", "ScriptScheme", "ScriptPhase", "ScriptReport",
 ]
 
 
@@ -63,6 +63,8 @@ class PressureSolver(enum.IntEnum):          # model.rs:148-152
     Multigrid = 2
     # the script's SOR in the script's own order (in place, row by row), one domain only
     SorLex = 4                               # 3 is unassigned (CFD_EINVAL, as before)
+    # the script's default solver, Jacobi with omega 0.7 (index.html:796-838), one domain only
+    JacobiScript = 5
 
 
 class VisualizationMode(enum.IntEnum):       # app.rs:505-509
@@ -180,6 +182,18 @@ class Residuals:                             # model.rs:23-32
     step_time: float                         # seconds (device time, HIP events)
     piso_substeps: int
     jacobi_sweeps_total: int = 0
+
+
+@dataclass
+class ScriptReport:                          # cfd_script_report: one log line of index.html:320-324
+    step_count: int                          # simulationStepCount after the step
+    substeps_run: int
+    substep_count_next: int
+    residual_u: float
+    residual_v: float
+    residual_p: float                        # (double)(float) of the script's
+    dt_next: float
+    inlet_velocity: float                    # currentInletVelocity of the step
 
 
 @dataclass
@@ -305,7 +319,7 @@ class Model:
         """The script's own substep (index.html pisoStep(dt_sub) with
         applyBoundaryConditions) in double over the f32 fields, `scheme` a
         ScriptScheme (QUICK included); the solve in the middle is the model's
-        (pressure_solver Multigrid or SorLex only).  Asynchronous."""
+        (pressure_solver Multigrid, SorLex or JacobiScript only).  Asynchronous."""
         s = self._script_step(dt_sub, scheme, inlet_velocity, inlet_profile)
         check("cfd_script_piso_step", load().cfd_script_piso_step(self._hh(), C.byref(s)))
 
@@ -314,6 +328,87 @@ class Model:
         """One pass of script_piso_step alone (ScriptPhase), synchronous."""
         s = self._script_step(dt_sub, scheme, inlet_velocity, inlet_profile)
         check("cfd_script_phase", load().cfd_script_phase(self._hh(), int(phase), C.byref(s)))
+
+    # ------------------------------------------- the script's time step
+    def _script_state_c(self, state: dict):
+        """cfd_script_state from {"dt", "substep_count", "step_count", "u_prev",
+        "v_prev"} (arrays optional); returns the struct and the arrays it points to."""
+        from ._lib import CfdScriptState
+        up = state.get("u_prev")
+        vp = state.get("v_prev")
+        keep = [None if a is None else np.ascontiguousarray(a, np.float32).ravel() for a in (up, vp)]
+        su, sv, _ = self._sizes()
+        for a, n in zip(keep, (su, sv)):
+            if a is not None and a.size != n:
+                raise ValueError("u_prev / v_prev have the sizes of u / v")
+        st = CfdScriptState(float(state.get("dt", 0.0)), int(state.get("substep_count", 5)),
+                            int(state.get("step_count", 0)), _fp(keep[0]), _fp(keep[1]))
+        return st, keep
+
+    def script_begin(self, state: Optional[dict] = None) -> None:
+        """Start (or restart) the script's time stepping (initSimulation,
+        index.html:218-228): dt unset, substepCount 5, step 0, uPrev / vPrev =
+        the current u, v -- or resume from `state` as script_state() returns it."""
+        if state is None:
+            check("cfd_script_begin", load().cfd_script_begin(self._hh(), None))
+            return
+        st, _keep = self._script_state_c(state)
+        check("cfd_script_begin", load().cfd_script_begin(self._hh(), C.byref(st)))
+
+    def script_state(self) -> dict:
+        """The script's step state (with get_state(), its checkpoint)."""
+        from ._lib import CfdScriptState
+        su, sv, _ = self._sizes()
+        up, vp = np.empty(su, np.float32), np.empty(sv, np.float32)
+        st = CfdScriptState(0.0, 0, 0, _fp(up), _fp(vp))
+        check("cfd_script_get_state", load().cfd_script_get_state(self._hh(), C.byref(st)))
+        return dict(dt=float(st.dt), substep_count=int(st.substep_count),
+                    step_count=int(st.step_count), u_prev=up, v_prev=vp)
+
+    def set_script_state(self, state: dict) -> None:
+        st, _keep = self._script_state_c(state)
+        check("cfd_script_set_state", load().cfd_script_set_state(self._hh(), C.byref(st)))
+
+    @staticmethod
+    def _script_report(r) -> "ScriptReport":
+        return ScriptReport(int(r.step_count), int(r.substeps_run), int(r.substep_count_next),
+                            float(r.residual_u), float(r.residual_v), float(r.residual_p),
+                            float(r.dt_next), float(r.inlet_velocity))
+
+    def script_update_n(self, n: int, scheme, target_inlet_velocity: float, dt_user: float,
+                        inlet_profile=InletProfile.Uniform) -> List["ScriptReport"]:
+        """n updateSimulation() calls of the script (index.html:261-363) on the
+        device, one ABI crossing; a report per step.  On CfdError the reports
+        filled so far are in the exception's `reports`."""
+        from ._lib import CfdScriptConfig, CfdScriptReport
+        n = int(n)
+        cfg = CfdScriptConfig(int(scheme), int(inlet_profile), float(target_inlet_velocity),
+                              float(dt_user))
+        out = (CfdScriptReport * max(n, 1))()
+        rc = load().cfd_script_update_n(self._hh(), C.byref(cfg), n, out)
+        reps = [self._script_report(r) for r in out[:max(n, 0)] if r.step_count]
+        try:
+            check("cfd_script_update_n", rc)
+        except CfdError as e:
+            e.reports = reps
+            raise
+        return reps
+
+    def script_update(self, scheme, target_inlet_velocity: float, dt_user: float,
+                      inlet_profile=InletProfile.Uniform) -> "ScriptReport":
+        """One updateSimulation() of the script, then its tracer tail while
+        tracers are enabled."""
+        from ._lib import CfdScriptConfig, CfdScriptReport
+        cfg = CfdScriptConfig(int(scheme), int(inlet_profile), float(target_inlet_velocity),
+                              float(dt_user))
+        out = CfdScriptReport()
+        rc = load().cfd_script_update(self._hh(), C.byref(cfg), C.byref(out))
+        try:
+            check("cfd_script_update", rc)
+        except CfdError as e:
+            e.reports = [self._script_report(out)] if out.step_count else []
+            raise
+        return self._script_report(out)
 
     def synchronize(self) -> None:
         check("cfd_synchronize", load().cfd_synchronize(self._hh()))

@@ -38,6 +38,8 @@ EXPORTS = [
     "cfd_tracers_set", "cfd_tracers_advance", "cfd_tracers_inject", "cfd_tracers_density",
     "cfd_run_set_tracers", "cfd_run_last_tracers",
     "cfd_script_piso_step", "cfd_script_phase",
+    "cfd_script_begin", "cfd_script_get_state", "cfd_script_set_state", "cfd_script_update",
+    "cfd_script_update_n",
 ]
 
 
@@ -58,6 +60,23 @@ class CfdParams(C.Structure):
 class CfdScriptStep(C.Structure):          # cfd_script_step
     _fields_ = [("scheme", C.c_int32), ("inlet_profile", C.c_int32),
                 ("inlet_velocity", C.c_double), ("dt_sub", C.c_double)]
+
+
+class CfdScriptConfig(C.Structure):        # cfd_script_config
+    _fields_ = [("scheme", C.c_int32), ("inlet_profile", C.c_int32),
+                ("target_inlet_velocity", C.c_double), ("dt_user", C.c_double)]
+
+
+class CfdScriptState(C.Structure):         # cfd_script_state
+    _fields_ = [("dt", C.c_double), ("substep_count", C.c_int32), ("step_count", C.c_uint64),
+                ("u_prev", C.POINTER(C.c_float)), ("v_prev", C.POINTER(C.c_float))]
+
+
+class CfdScriptReport(C.Structure):        # cfd_script_report
+    _fields_ = [("step_count", C.c_uint64), ("substeps_run", C.c_int32),
+                ("substep_count_next", C.c_int32), ("residual_u", C.c_double),
+                ("residual_v", C.c_double), ("residual_p", C.c_double), ("dt_next", C.c_double),
+                ("inlet_velocity", C.c_double)]
 
 
 class CfdResiduals(C.Structure):
@@ -217,6 +236,12 @@ def load():
         # tracer particles
         "cfd_script_piso_step": (i32, [vp, C.POINTER(CfdScriptStep)]),
         "cfd_script_phase": (i32, [vp, i32, C.POINTER(CfdScriptStep)]),
+        "cfd_script_begin": (i32, [vp, C.POINTER(CfdScriptState)]),
+        "cfd_script_get_state": (i32, [vp, C.POINTER(CfdScriptState)]),
+        "cfd_script_set_state": (i32, [vp, C.POINTER(CfdScriptState)]),
+        "cfd_script_update": (i32, [vp, C.POINTER(CfdScriptConfig), C.POINTER(CfdScriptReport)]),
+        "cfd_script_update_n": (i32, [vp, C.POINTER(CfdScriptConfig), i32,
+                                      C.POINTER(CfdScriptReport)]),
         "cfd_tracers_enable": (i32, [vp, C.c_uint64, i32]),
         "cfd_tracers_disable": (i32, [vp]),
         "cfd_tracers_count": (i32, [vp, C.POINTER(C.c_uint64)]),

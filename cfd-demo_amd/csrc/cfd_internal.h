@@ -331,6 +331,15 @@ size_t sor_lex_words(int iters, int ny);
 hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
                           Ctl *ctl, uint32_t *pol, uint32_t *exitw, uint32_t *host_fail, int pass,
                           int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s);
+// The script's Jacobi, omega 0.7 (cfd_jacobi_script.hip, pressure_solver 5):
+// one whole iteration per launch -- interior update, max |new - old| into
+// err_slots' set `it`, boundary copies -- ping-pong between pa / pb from
+// ctl->cur exactly as launch_sor_fused (it = 0 reads nothing); with tol the
+// launch returns at once when iteration it - 1 fell below p_tol.  nx even,
+// ny >= 3, whole domain.
+void launch_jacobi_script(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
+                          Ctl *ctl, uint32_t *err_slots, int pass, int it, int tol, float p_tol,
+                          int res, hipStream_t s);
 void launch_mg_smooth(const MgLevel &L, const float *src, float *dst, const Ctl *ctl, int pass,
                       hipStream_t s);
 // Five smoothing sweeps src -> dst in one launch (temporal blocking: one
@@ -435,6 +444,23 @@ void launch_script_predict(const Geom &g, const Fields &f, const ScriptStep &k, 
                            hipStream_t s);
 // u, v from u*, v* and the current p', p += p', then the boundary pass (:842-866, :870-930)
 void launch_script_correct(const Geom &g, const Fields &f, const ScriptStep &k, hipStream_t s);
+
+// ---- one updateSimulation() around the substeps (cfd_script_update.hip;
+// index.html:261-363) ----
+// The step's reduction block, 64-bit words: three spread maxima of doubles as
+// their bits (max |u - uOld|, max |v - vOld|, max(|u|, |v|); kResSlots slots
+// each, one 64-byte line per slot), then one line whose first f32 is the
+// running maximum of the substeps' pressure residuals.  Zeroed by the host (in
+// stream order) when a step starts, read back once when it ends.
+constexpr int kScrRedStride = 8;
+constexpr int kScrRedPmax = 3 * kResSlots * kScrRedStride;
+constexpr int kScrRedWords = kScrRedPmax + kScrRedStride;
+// nu, nv: elements of u and v (one domain: contiguous from local row 0)
+void launch_script_begin(const Fields &f, float *u_prev, float *u_old, float *v_prev, float *v_old,
+                         long nu, long nv, int extrapolate, hipStream_t s);
+void launch_script_pmax(const Fields &f, unsigned long long *red, hipStream_t s);
+void launch_script_end(const Fields &f, float *u_prev, const float *u_old, float *v_prev,
+                       const float *v_old, long nu, long nv, unsigned long long *red, hipStream_t s);
 
 // Jacobi kernel geometry (exported for the roofline bookkeeping in bench).
 constexpr int kJacRowsPerWave = 16;

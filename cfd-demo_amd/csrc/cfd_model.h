@@ -13,10 +13,11 @@
 // launch goes through the launch_* functions of cfd_internal.h):
 //   cfd_model_comm.hip     halo exchanges, all-reduce, RCCL deadlines, LocalHub
 //   cfd_model_jacobi.hip   the Jacobi solve: single domain, slabs, speculative
-//   cfd_model_solvers.hip  SOR (red-black, script order) and multigrid
+//   cfd_model_solvers.hip  SOR (red-black, script order), the script's Jacobi and multigrid
 //   cfd_model_step.hip     piso_step, update, graph capture, sync, checkpoint
 //   cfd_model_build.hip    options, validation, creation, destruction
 //   cfd_model_extras.hip   tracer particles and the script's substep
+//   cfd_model_script.hip   the script's time step (updateSimulation) around that substep
 //   cfd_model_abi.hip      the remaining extern "C" surface
 #pragma once
 
@@ -309,6 +310,21 @@ struct cfd_model {
     double scr_inlet_v = 0.0;
     int scr_inlet_profile = -1;   // -1: nothing uploaded yet
 
+    // ------------------ the script's time step (cfd_model_script.hip)
+    // One allocation at the first cfd_script_begin: uPrev, vPrev, uOld, vOld,
+    // then the step's reduction block (cfd_internal.h kScrRedWords); su_h is
+    // its pinned host copy.  The host scalars are the script's globals.
+    char *su_pool = nullptr;
+    float *su_uprev = nullptr, *su_vprev = nullptr, *su_uold = nullptr, *su_vold = nullptr;
+    unsigned long long *su_red = nullptr, *su_h = nullptr;
+    bool su_begun = false, su_bad = false;
+    bool su_failed = false;       // an update failed after its begin pass: u, v are mid-step
+    bool su_dt_set = false;       // false: the first update takes dt_user (`let dt` is the input's value)
+    double su_dt = 0.0;           // let dt
+    int32_t su_substeps = 5;      // let substepCount
+    uint64_t su_steps = 0;        // simulationStepCount
+    double su_inlet = 0.0;        // currentInletVelocity
+
     // ============================================================ methods
     bool sharded() const { return n_ranks > 1; }
     size_t u_rows_alloc() const { return (size_t)g.nyl + 2 * cfd::kGhostUV; }
@@ -367,6 +383,7 @@ struct cfd_model {
     int enqueue_sor_sharded(const cfd::SorConst &k, int pass, float *residual_out, hipEvent_t e0);
     int enqueue_sor_sharded_deep(const cfd::SorConst &k, int pass, hipEvent_t e0);
     int enqueue_sor_lex(int pass);
+    int enqueue_jacobi_script(int pass);
     void mg_rows(int l, int r, int *j0o, int *j1o) const;
     int mg_partition_levels(const std::vector<std::pair<int, int>> &dims, int tail) const;
     int mg_build();
@@ -405,6 +422,11 @@ struct cfd_model {
     bool scr_in_obstacle(double x, double y) const;
     int script_build();
     int script_prepare(const cfd_script_step *s, cfd::ScriptStep *out);
+    int script_substep(const cfd_script_step *s);
+
+    // ---- cfd_model_script.hip
+    int su_alloc();
+    int su_update(const cfd_script_config *c, cfd_script_report *out);
 
     // ---- cfd_model_build.hip
     void destroy();
@@ -419,6 +441,8 @@ void apply_params(cfd_model *m, const cfd_params *p);
 void set_sums_track(cfd_model *m);
 int create_model(const cfd_grid *grid, const cfd_params *params, int device, int n_ranks, int rank,
                  const void *uid, LocalHub *hub, cfd_model **out);
+// ---- cfd_model_extras.hip: the argument and model checks of cfd_script_piso_step
+int script_check(cfd_model *m, const cfd_script_step *s);
 // ---- cfd_model_comm.hip
 int comm_init(cfd_model *m, const ncclUniqueId &id, int n_ranks, int rank);
 // ---- cfd_model_jacobi.hip

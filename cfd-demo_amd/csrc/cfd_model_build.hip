@@ -54,10 +54,10 @@ int validate(const cfd_grid *grid, const cfd_params *p) {
     if (p->inlet_profile != 0 && p->inlet_profile != 1)
         return fail(CFD_EINVAL, "inlet_profile must be 0 or 1");
     // 3 is unassigned: it was rejected before CFD_SOLVER_SOR_LEX existed and stays so
-    if (p->pressure_solver < CFD_SOLVER_JACOBI || p->pressure_solver > CFD_SOLVER_SOR_LEX ||
+    if (p->pressure_solver < CFD_SOLVER_JACOBI || p->pressure_solver > CFD_SOLVER_JACOBI_SCRIPT ||
         p->pressure_solver == 3)
-        return fail(CFD_EINVAL, "pressure_solver must be 0 (Jacobi), 1 (SOR), 2 (multigrid) or "
-                                "4 (SOR in the script's order)");
+        return fail(CFD_EINVAL, "pressure_solver must be 0 (Jacobi), 1 (SOR), 2 (multigrid), "
+                                "4 (SOR in the script's order) or 5 (the script's Jacobi)");
     if (p->bc_kind != 0 && p->bc_kind != 1) return fail(CFD_EINVAL, "bc_kind must be 0 or 1");
     return 0;
 }
@@ -70,6 +70,9 @@ int validate_sharded(const cfd_model *m, const cfd_params *p) {
     if (m->n_ranks > 1 && p->pressure_solver == CFD_SOLVER_SOR_LEX)
         return fail(CFD_EINVAL, "pressure_solver 4 (SOR in the script's order) runs on one domain "
                                 "only: sharded models take 0, 1 or 2");
+    if (m->n_ranks > 1 && p->pressure_solver == CFD_SOLVER_JACOBI_SCRIPT)
+        return fail(CFD_EINVAL, "pressure_solver 5 (the script's Jacobi) runs on one domain only: "
+                                "sharded models take 0, 1 or 2");
     if (m->n_ranks <= 1 || p->pressure_solver != CFD_SOLVER_SOR) return 0;
     const int lo = std::max(0, 1 - (int)m->j0);
     const int hi = std::min((int)(m->j1 - m->j0), (int)m->grid.ny - 1 - (int)m->j0);
@@ -426,6 +429,9 @@ int create_model(const cfd_grid *grid, const cfd_params *params, int device, int
     if (n_ranks > 1 && params->pressure_solver == CFD_SOLVER_SOR_LEX)   // before any device call
         return fail(CFD_EINVAL, "pressure_solver 4 (SOR in the script's order) runs on one domain "
                                 "only: sharded models take 0, 1 or 2");
+    if (n_ranks > 1 && params->pressure_solver == CFD_SOLVER_JACOBI_SCRIPT)
+        return fail(CFD_EINVAL, "pressure_solver 5 (the script's Jacobi) runs on one domain only: "
+                                "sharded models take 0, 1 or 2");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(CFD_EHIP, "no HIP device available");
@@ -508,6 +514,8 @@ void cfd_model::destroy() {
     if (trc_pool) (void)hipFree(trc_pool);
     if (trc_dens) (void)hipFree(trc_dens);
     if (scr_pool) (void)hipFree(scr_pool);
+    if (su_pool) (void)hipFree(su_pool);
+    if (su_h) (void)hipHostFree(su_h);
     drop_graph();
     for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
     if (ev_step0) (void)hipEventDestroy(ev_step0);

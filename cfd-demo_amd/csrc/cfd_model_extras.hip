@@ -271,7 +271,9 @@ int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny) {
 }
 
 // ---- the script's substep (index.html:366-930; kernels in cfd_script_step.hip) ----
-namespace {
+}  // extern "C"
+
+namespace cfd {
 
 int script_check(cfd_model *m, const cfd_script_step *s) {
     if (!m) return fail(CFD_EINVAL, "null model");
@@ -281,9 +283,11 @@ int script_check(cfd_model *m, const cfd_script_step *s) {
     if (m->params.bc_kind != CFD_BC_CHANNEL)
         return fail(CFD_EINVAL, "the script substep has the channel boundary conditions only");
     if (m->params.pressure_solver != CFD_SOLVER_MULTIGRID &&
-        m->params.pressure_solver != CFD_SOLVER_SOR_LEX)
-        return fail(CFD_EINVAL, "the script substep needs pressure_solver 2 (multigrid) or 4 "
-                                "(script-order SOR): the others are not the script's");
+        m->params.pressure_solver != CFD_SOLVER_SOR_LEX &&
+        m->params.pressure_solver != CFD_SOLVER_JACOBI_SCRIPT)
+        return fail(CFD_EINVAL, "the script substep needs pressure_solver 2 (multigrid), 4 "
+                                "(script-order SOR) or 5 (the script's Jacobi): the others are not "
+                                "the script's");
     if (s->scheme != CFD_SCRIPT_FIRST && s->scheme != CFD_SCRIPT_SECOND && s->scheme != CFD_SCRIPT_QUICK)
         return fail(CFD_EINVAL, "script scheme must be 0 (first), 1 (second) or 2 (quick)");
     if (s->inlet_profile != CFD_INLET_UNIFORM && s->inlet_profile != CFD_INLET_PARABOLIC)
@@ -296,13 +300,15 @@ int script_check(cfd_model *m, const cfd_script_step *s) {
     return 0;
 }
 
-}  // namespace
+}  // namespace cfd
 
-int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s) {
-    if (int rc = script_check(m, s)) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    if (int rc = m->invalidate_sums()) return rc;
-    if (int rc = m->ck_begin()) return rc;
+// one checked substep, enqueued: cfd_script_piso_step's body, and each substep
+// of cfd_script_update
+int cfd_model::script_substep(const cfd_script_step *s) {
+    HIP_TRY(hipSetDevice(device));
+    if (int rc = invalidate_sums()) return rc;
+    if (int rc = ck_begin()) return rc;
+    cfd_model *m = this;
     const cfd_script_step st = *s;
     auto run = [m, st]() {
         ScriptStep k;
@@ -316,6 +322,13 @@ int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s) {
     };
     m->ck_record(run);
     return run();
+}
+
+extern "C" {
+
+int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s) {
+    if (int rc = script_check(m, s)) return rc;
+    return m->script_substep(s);
 }
 
 int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s) {

@@ -109,6 +109,7 @@ int cfd_model::enqueue_solve(int pass) {
     if (params.pressure_solver == CFD_SOLVER_SOR) return enqueue_sor(pass);
     if (params.pressure_solver == CFD_SOLVER_MULTIGRID) return enqueue_mg(pass);
     if (params.pressure_solver == CFD_SOLVER_SOR_LEX) return enqueue_sor_lex(pass);
+    if (params.pressure_solver == CFD_SOLVER_JACOBI_SCRIPT) return enqueue_jacobi_script(pass);
     if (!sharded()) return enqueue_jacobi_single(pass);
     if (g.tol_enabled && spec_slab_ok()) return enqueue_spec_slabs(pass);
     return enqueue_jacobi_slabs(pass);

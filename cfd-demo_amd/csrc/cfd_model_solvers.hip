@@ -234,6 +234,34 @@ int cfd_model::enqueue_sor_lex(int pass) {
     return 0;
 }
 
+// The script's default solver, Jacobi with omega 0.7 (index.html:796-838;
+// cfd_jacobi_script.hip): one launch per iteration, ping-pong from the
+// device's current buffer, launches after the early exit predicated on the
+// device; the finalize flips the buffer once per iteration run, as in the
+// fused red-black solve.  One domain only (validate_sharded).
+int cfd_model::enqueue_jacobi_script(int pass) {
+    const int iters = params.jacobi_iters;
+    if (sharded()) return fail(CFD_EINVAL, "pressure_solver 5 (the script's Jacobi) runs on one domain only");
+    hipEvent_t e0;
+    begin_solve_timing(pass, &e0);
+    int launches = iters;
+    if (iters < 1) {
+        // p' = 0 (index.html:798) in whichever buffer is current
+        launch_fill_zero(f.pp[0], (size_t)g.nx * g.ny, f.ctl, pass, stream);
+        launch_fill_zero(f.pp[1], (size_t)g.nx * g.ny, f.ctl, pass, stream);
+        launches = 2;
+    }
+    const SorConst k = sor_consts();
+    for (int it = 0; it < iters; ++it)
+        launch_jacobi_script(f.pp[0], f.pp[1], f.rhs, g.nx, g.ny, k, f.ctl, f.err_slots, pass, it,
+                             g.tol_enabled, g.p_tol, g.tol_enabled || it == iters - 1, stream);
+    end_solve_timing(e0, (uint64_t)iters, (uint64_t)launches);
+    launch_finalize_solve(g, f, pass, iters, pass >= 1 ? 1 : 0, iters, stream);
+    if (!g.tol_enabled) host_cur = (host_cur + iters) & 1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Level table of mgVcycle's recursion: sizes floor((n+1)/2) down to the
 // first level with nx <= 4 or ny <= 4 (index.html:1444-1451), spacing
 // doubling per level (:1458).

@@ -125,8 +125,30 @@ enum { CFD_INLET_UNIFORM = 0, CFD_INLET_PARABOLIC = 1 };
  * waits are bounded like the persistent Jacobi solve's
  * (CFD_PERSIST_DEADLINE_US): past the deadline the next synchronising call
  * returns CFD_ETIMEOUT and p' is invalid until cfd_set_state (no checkpoint
- * is kept for this solver). */
-enum { CFD_SOLVER_JACOBI = 0, CFD_SOLVER_SOR = 1, CFD_SOLVER_MULTIGRID = 2, CFD_SOLVER_SOR_LEX = 4 };
+ * is kept for this solver).
+ * JACOBI_SCRIPT (value 5) is the script's default solver, its Jacobi branch
+ * (index.html:796-838): p' restarts from 0; per iteration, over the interior,
+ *   new = 0.7 * ((E + W)/(dx*dx) + (N + S)/(dy*dy) - rhs) / denom + (1 - 0.7) * old
+ * with denom = 2/dx2 + 2/dy2 as :181-183 builds it, every operation in double
+ * in the script's order ((1 - 0.7) is the double 0.30000000000000004) and one
+ * rounding to f32 on the store; maxError = max |new - old| over the interior,
+ * on the stored values widened, NaN ignored; then the interior is copied back,
+ * rows 0 / ny-1 take rows 1 / ny-2 over all columns, column 0 takes column 1
+ * and column nx-1 is 0 over all rows, in that order (:828-835).  The iterates
+ * are the script's bit for bit (tests/golden/js_jac_*.npz).  Conventions as
+ * SOR_LEX: jacobi_iters iterations (the script's 50) with the early exit at
+ * p_tol when tol_enabled (the script's 1e-6), (float)maxError of the last
+ * iteration run reported, jacobi_sweeps_total grows by the iterations run, and
+ * the same sliver: the script tests the double against the double 1e-6, this
+ * library the float against the float p_tol.  One domain only, as SOR_LEX.  On
+ * the GPU one iteration is one launch (cfd_jacobi_script.hip: update, maximum
+ * and boundary copies; p' ping-pongs), the exit is decided on the device and no
+ * workgroup waits for another, so it has no deadline and cannot time out.
+ * With jacobi_iters 0 (the script's count is a constant 50) p' is 0 and the
+ * reported residual is 0, as for SOR_LEX, where the script's branch would leave
+ * lastPResidual = Infinity (:801, :838). */
+enum { CFD_SOLVER_JACOBI = 0, CFD_SOLVER_SOR = 1, CFD_SOLVER_MULTIGRID = 2, CFD_SOLVER_SOR_LEX = 4,
+       CFD_SOLVER_JACOBI_SCRIPT = 5 };
 enum { CFD_BC_CHANNEL = 0, CFD_BC_CAVITY = 1 };
 typedef struct {
     float dt;
@@ -437,11 +459,11 @@ int cfd_tracers_density(cfd_model *m, uint32_t *counts_nx_ny);
  * boundary pass runs in the script's order (inlet, outlet copy, rows 0 and
  * ny-1 of u, rows 0 and ny of v, obstacle faces).
  * The solve between the two passes is the model's own, unchanged, and must be
- * one of the two pinned to the script: pressure_solver CFD_SOLVER_MULTIGRID or
- * CFD_SOLVER_SOR_LEX (both restart p' from 0); any other returns CFD_EINVAL
- * (the script's omega 0.7 Jacobi is not implemented; the red-black SOR and the
- * Rust Jacobi are not the script's).  Its settings come from cfd_params (the
- * script's own: jacobi_iters 50, tol_enabled 1, p_tol 1e-4); its residual lands
+ * one of the three pinned to the script: pressure_solver CFD_SOLVER_MULTIGRID,
+ * CFD_SOLVER_SOR_LEX or CFD_SOLVER_JACOBI_SCRIPT (all restart p' from 0); any
+ * other returns CFD_EINVAL (the red-black SOR and the Rust Jacobi are not the
+ * script's).  Its settings come from cfd_params (the script's own: jacobi_iters
+ * 50, tol_enabled 1, p_tol 1e-4, or 1e-6 for its Jacobi); its residual lands
  * in cfd_get_state().last_p_residual and jacobi_sweeps_total grows as the solve
  * makes it grow.  simulation_step, dt and the u / v residuals are not touched:
  * like cfd_piso_step this is the substep, not updateSimulation (the caller
@@ -467,6 +489,91 @@ int cfd_script_piso_step(cfd_model *m, const cfd_script_step *s);
 enum { CFD_SCRIPT_PHASE_PREDICT = 0,   /* :368-739  u*, v*, rhs             */
        CFD_SCRIPT_PHASE_CORRECT = 1 }; /* :842-866  u, v, p += p', then BCs */
 int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s);
+
+/* ---- the script's time step (index.html:261-363 updateSimulation with
+ * :1322-1342 computeAutomaticTimeStep, then simulationLoop's tracer tail
+ * :1233-1238) ----
+ * One cfd_script_update is one updateSimulation(), in the script's order:
+ *   extrapolate  (step_count > 0) u = 2u - uPrev, v = 2v - vPrev, each stored as
+ *                (float)(2.0 * (double)u - (double)uPrev);
+ *   save         uOld = u, vOld = v;
+ *   ramp         currentInletVelocity = step_count < 1000
+ *                ? (step_count / 1000) * target : target (:277-281);
+ *   substeps     substep_count runs of cfd_script_piso_step's path with
+ *                dt_sub = dt / substep_count, enqueued back to back, the running
+ *                maximum of their pressure residuals kept on the device;
+ *   residuals    max |u - uOld|, max |v - vOld| and maxVel = max(|u|, |v|), in
+ *                double, NaN ignored as the script's `>` ignores it;
+ *   save         uPrev = u, vPrev = v.
+ * That is two fused passes of new device work around the substeps' launches
+ * (k_script_begin, k_script_end) and one word folded after each solve
+ * (k_script_pmax); no field crosses PCIe.  Then ONE synchronisation and one
+ * small read-back per step (dt_sub and the substep count are kernel arguments
+ * and host loop bounds of the substep), after which the host applies the
+ * script's rules in C double, JavaScript's number: step_count++, the substep
+ * rule of :310-317 (ceil, floor, the cap 20, the floor 1),
+ * computeAutomaticTimeStep (its maxVel === 0 return of dt_user included) and
+ * the 1.1 x previous dt limit.  While tracers are enabled each update ends as
+ * simulationLoop does: cfd_tracers_advance(dt_next) -- the script passes the
+ * dt it has just computed -- then cfd_tracers_inject() iff step_count %
+ * interval == 0 after the increment.
+ * The pressure residual is the library's, (double)(float)maxError, where the
+ * script holds the double.  Rounding is monotone, so the maximum over the
+ * substeps commutes with it, and the substep and dt decisions can differ from
+ * the script's only when that rounding moves errorNorm across 1e-3, across
+ * 1e-4, or across an integer boundary of substepCount * errorNorm / 1e-3 (the
+ * sliver note of CFD_SOLVER_SOR_LEX above, one level up); no committed fixture
+ * (tests/golden/js_update_*.npz, the script's own numbers under node) is in
+ * it.  residualScalingEnabled (off on the page) is not implemented: it scales
+ * dt by the double residual.
+ * State: uPrev, vPrev, uOld, vOld on the device and the script's dt,
+ * substepCount, simulationStepCount and currentInletVelocity on the host, all
+ * allocated by the first cfd_script_begin.  simulation_step, dt and the u / v
+ * residuals of the Rust-path state (cfd_get_state) are not touched, cfd_update
+ * never takes this path, and steps that use it are not replayed from a
+ * captured graph.
+ * CFD_EINVAL as cfd_script_piso_step gives it (a sharded model, the cavity, a
+ * pressure_solver that is not 2, 4 or 5, a bad scheme or profile), and for a
+ * non-finite or non-positive dt_user, a non-finite target and n < 1;
+ * CFD_ESTATE before cfd_script_begin; CFD_ENONFINITE, with the report filled,
+ * when a residual or dt_next comes out non-finite or dt_next <= 0 (the script
+ * would go on dividing by it): further updates then return CFD_ENONFINITE
+ * until cfd_script_begin or cfd_script_set_state.  An update that fails for
+ * another reason after its first pass was enqueued (a solve's CFD_ETIMEOUT, a
+ * HIP error) leaves u and v extrapolated or part-way through the substeps and
+ * the script's scalars unchanged; a retry would extrapolate twice, so further
+ * updates return CFD_ESTATE until the caller has restored the fields
+ * (cfd_set_state) and called cfd_script_begin or cfd_script_set_state. */
+typedef struct {            /* what the page's controls hold when the step starts */
+    int32_t scheme;         /* CFD_SCRIPT_FIRST / SECOND / QUICK */
+    int32_t inlet_profile;  /* CFD_INLET_UNIFORM / CFD_INLET_PARABOLIC */
+    double  target_inlet_velocity;  /* inletVelocitySlider */
+    double  dt_user;                /* parseFloat(timeStepInput.value) */
+} cfd_script_config;
+typedef struct {            /* the script's step state; also its checkpoint (with cfd_get_state) */
+    double   dt;            /* let dt; 0: unset, the next update takes dt_user */
+    int32_t  substep_count; /* let substepCount (5 at page load), in [1, 20] */
+    uint64_t step_count;    /* simulationStepCount */
+    float   *u_prev, *v_prev;       /* (nx+1)*ny and nx*(ny+1) floats; NULL skips */
+} cfd_script_state;
+typedef struct {            /* one log line of :320-324 plus the new dt */
+    uint64_t step_count;    /* after the increment */
+    int32_t  substeps_run, substep_count_next;
+    double   residual_u, residual_v, residual_p, dt_next, inlet_velocity;
+} cfd_script_report;
+/* st NULL: initSimulation (:218-228) -- dt unset, substep_count 5, step 0,
+ * uPrev / vPrev = the model's current u, v.  Else as cfd_script_set_state, with
+ * uPrev / vPrev = the model's current u, v where a pointer is NULL.
+ * Synchronises; clears CFD_ENONFINITE of this path. */
+int cfd_script_begin(cfd_model *m, const cfd_script_state *st);
+/* Scalars, and uPrev / vPrev into the caller's arrays.  Synchronises. */
+int cfd_script_get_state(cfd_model *m, cfd_script_state *st);
+/* CFD_EINVAL for a negative or non-finite dt and substep_count outside [1, 20]. */
+int cfd_script_set_state(cfd_model *m, const cfd_script_state *st);
+int cfd_script_update(cfd_model *m, const cfd_script_config *c, cfd_script_report *out);
+/* n updates (the loop, so that a binding crosses the ABI once); out_n: n
+ * records or NULL.  Stops at the first failing update. */
+int cfd_script_update_n(cfd_model *m, const cfd_script_config *c, int n, cfd_script_report *out_n);
 
 /* The grid and parameters the model runs with (NULL skips either). */
 int cfd_get_config(const cfd_model *m, cfd_grid *grid, cfd_params *params);
