@@ -523,6 +523,11 @@ int cfd_polygon_new(const cfd_point *vertex_buffer, size_t n_points, const uint6
     }
     for (size_t k = 0; k < n_vertices; ++k)
         if (vertices[k] >= n_points) return err(CFD_EINVAL, "vertex index out of range (reference panics)");
+    // edges() (polygon.rs:188-197) also reads vertex_buffer[(i + 1) % vertices.len()]
+    for (size_t k = 0; k < n_vertices; ++k)
+        if ((vertices[k] + 1) % n_vertices >= n_points)
+            return err(CFD_EINVAL, "edge end index (i + 1) % vertices.len() out of range "
+                                   "(reference panics in edges())");
     cfd_polygon *p = new cfd_polygon();
     p->vb.assign(vertex_buffer, vertex_buffer + n_points);
     p->verts.assign(vertices, vertices + n_vertices);

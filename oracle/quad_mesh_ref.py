@@ -182,7 +182,17 @@ class Polygon:
     def __init__(self, vertex_buffer, vertices):       # new :19-40
         if len(vertices) < 3:
             raise PolygonError("NotEnoughVertices")
-        pts = [vertex_buffer[i] for i in vertices]
+        # the reference panics (index out of bounds) on these: in new for i
+        # itself, in edges() for (i + 1) % vertices.len().  Refused up front,
+        # as the product does (CFD_EINVAL from cfd_polygon_new).
+        n_pts, n = len(vertex_buffer), len(vertices)
+        for i in vertices:
+            if not 0 <= i < n_pts:
+                raise IndexError("vertex index out of range (reference panics)")
+            if (i + 1) % n >= n_pts:
+                raise IndexError("edge end index (i + 1) % vertices.len() out of range "
+                                 "(reference panics in edges())")
+        pts =[vertex_buffer[i] for i in vertices]
         if polygon_is_self_intersecting(pts):
             raise PolygonError("SelfIntersecting")
         self.vertex_buffer = list(vertex_buffer)
