@@ -19,7 +19,9 @@ any fixture lies where the two comparisons differ.
     python tests/golden/make_js_sor_golden.py [NAME ...]
 
 Only fixtures whose .npz is missing are generated; the seed of a case is
-5151 + its position in CASES.
+5151 + its position in CASES, unless the case names a row of the seam tests'
+table (tests/_sor_lex_cases.py), whose rhs recipe (seed, scale, rows kept) it
+then takes.
 """
 import json
 import os
@@ -31,12 +33,13 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+import _sor_lex_cases as seams   # noqa: E402
 import _sor_lex_ref as ref   # noqa: E402
 
 REF_HTML = "/root/reference/index.html"
 
 # name -> (nx, ny, lx, ly, iterations, rhs scale, expected exit: None no early
-# exit, 0 / 1 early exit at an even / odd count)
+# exit, 0 / 1 early exit at an even / odd count[, the seam table's case])
 CASES = {
     "js_sor_16x4": (16, 4, 30.0, 10.0, 5, 100.0, None),
     "js_sor_16x5": (16, 5, 30.0, 10.0, 9, 100.0, None),
@@ -50,6 +53,12 @@ CASES = {
     "js_sor_16x200": (16, 200, 30.0, 10.0, 10, 100.0, None),               # skew longer than a row
     "js_sor_64x48_it1": (64, 48, 4.0 / 3.0, 1.0, 1, 100.0, None),
     "js_sor_64x48_it2": (64, 48, 4.0 / 3.0, 1.0, 2, 100.0, None),
+    # exits on more than one band (test_sor_lex_seams_cpu.py says what each is built for)
+    "js_sor_24x132_exit_first_band": (24, 132, 30.0, 10.0, 100, 0.03, 1, "first_band"),
+    "js_sor_24x132_exit_last_band": (24, 132, 30.0, 10.0, 100, 0.03, 1, "last_band_s0.03"),
+    "js_sor_32x195_exit_it1": (32, 195, 30.0, 10.0, 100, 0.01, 1, "four_bands_first_iteration"),
+    "js_sor_16x67_exit_one_row_band": (16, 67, 30.0, 10.0, 100, 0.01, 0,
+                                       "one_row_band_tests_first_band"),
 }
 
 HARNESS = r"""
@@ -97,7 +106,8 @@ def main(only=()):
                               subprocess.run(["node", "--version"], capture_output=True,
                                              text=True).stdout.strip(),
                     "fixtures": {}}
-    for k, (name, (nx, ny, lx, ly, iters, scale, exit_parity)) in enumerate(CASES.items()):
+    for k, (name, case) in enumerate(CASES.items()):
+        nx, ny, lx, ly, iters, scale, exit_parity = case[:7]
         if only and name not in only:
             continue
         if os.path.exists(os.path.join(HERE, name + ".npz")):
@@ -106,8 +116,13 @@ def main(only=()):
             continue
         dx = np.float32(lx) / np.float32(nx)
         dy = np.float32(ly) / np.float32(ny)
-        rng = np.random.default_rng(5151 + k)
-        rhs = (rng.uniform(-1, 1, nx * ny) * scale).astype(np.float32)
+        seed, rows = 5151 + k, None
+        if len(case) > 7:
+            row = seams.BY_NAME[case[7]]
+            assert (row.nx, row.ny, row.lx, row.ly, row.iters, row.scale, row.tol, seams.P_TOL) == \
+                (nx, ny, lx, ly, iters, scale, True, 1e-4), name
+            seed, rows = row.seed, row.rows
+        rhs = seams.make_rhs(nx, ny, seed, scale, rows)
         with tempfile.TemporaryDirectory() as d:
             for fn, txt in (("branch.js", branch), ("harness.js", HARNESS)):
                 open(os.path.join(d, fn), "w").write(txt)
@@ -132,7 +147,9 @@ def main(only=()):
                             iters_run=np.array([n_run], np.int64))
         manifest["fixtures"][name] = {"nx": nx, "ny": ny, "lx": lx, "ly": ly, "dx": float(dx),
                                       "dy": float(dy), "iterations": iters, "rhs_scale": scale,
-                                      "iters_run": n_run, "seed": 5151 + k}
+                                      "iters_run": n_run, "seed": seed}
+        if rows is not None:
+            manifest["fixtures"][name]["rhs_rows"] = list(rows)
         print(name, "iterations run", n_run, "residual", res)
     json.dump(manifest, open(mpath, "w"), indent=1)
 

@@ -19,7 +19,10 @@ JS = json.load(open(os.path.join(GOLD, "js_sor_manifest.json")))["fixtures"]
 
 REQUIRED = {"js_sor_16x4", "js_sor_16x5", "js_sor_24x7_p2", "js_sor_40x24_exit_even",
             "js_sor_32x12_exit_odd", "js_sor_72x66", "js_sor_72x67", "js_sor_136x132",
-            "js_sor_128x128_p2", "js_sor_16x200", "js_sor_64x48_it1", "js_sor_64x48_it2"}
+            "js_sor_128x128_p2", "js_sor_16x200", "js_sor_64x48_it1", "js_sor_64x48_it2",
+            # exits on more than one band (tests/_sor_lex_cases.py)
+            "js_sor_24x132_exit_first_band", "js_sor_24x132_exit_last_band",
+            "js_sor_32x195_exit_it1", "js_sor_16x67_exit_one_row_band"}
 
 
 def test_fixture_set_is_complete():
