@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -368,6 +368,32 @@ class Model:
     def set_script_state(self, state: dict) -> None:
         st, _keep = self._script_state_c(state)
         check("cfd_script_set_state", load().cfd_script_set_state(self._hh(), C.byref(st)))
+
+    def script_options(self, residual_f64: Optional[bool] = None,
+                       residual_scaling: Optional[bool] = None) -> dict:
+        """Set (where not None) and return the script path's options.
+        residual_f64: solves 2, 4 and 5 publish the script's double residual and
+        script_update decides from it; residual_scaling: the page's "residual
+        scaling" checkbox (index.html:338-348), which implies residual_f64."""
+        from ._lib import CfdScriptOptions
+        o = CfdScriptOptions()
+        check("cfd_script_get_options", load().cfd_script_get_options(self._hh(), C.byref(o)))
+        if residual_f64 is not None or residual_scaling is not None:
+            if residual_f64 is not None:
+                o.residual_f64 = int(residual_f64)
+            if residual_scaling is not None:
+                o.residual_scaling = int(residual_scaling)
+            check("cfd_script_set_options", load().cfd_script_set_options(self._hh(), C.byref(o)))
+            check("cfd_script_get_options", load().cfd_script_get_options(self._hh(), C.byref(o)))
+        return dict(residual_f64=int(o.residual_f64), residual_scaling=int(o.residual_scaling))
+
+    def p_residual_f64(self) -> Tuple[float, float]:
+        """(last, step_max): the last solve's double residual and the maximum
+        over the substeps of the last script_update (residual_f64 on)."""
+        last, smax = C.c_double(), C.c_double()
+        check("cfd_get_p_residual_f64",
+              load().cfd_get_p_residual_f64(self._hh(), C.byref(last), C.byref(smax)))
+        return float(last.value), float(smax.value)
 
     @staticmethod
     def _script_report(r) -> "ScriptReport":

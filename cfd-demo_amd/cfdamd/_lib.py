@@ -40,6 +40,7 @@ EXPORTS = [
     "cfd_script_piso_step", "cfd_script_phase",
     "cfd_script_begin", "cfd_script_get_state", "cfd_script_set_state", "cfd_script_update",
     "cfd_script_update_n",
+    "cfd_script_set_options", "cfd_script_get_options", "cfd_get_p_residual_f64",
 ]
 
 
@@ -77,6 +78,10 @@ class CfdScriptReport(C.Structure):        # cfd_script_report
                 ("substep_count_next", C.c_int32), ("residual_u", C.c_double),
                 ("residual_v", C.c_double), ("residual_p", C.c_double), ("dt_next", C.c_double),
                 ("inlet_velocity", C.c_double)]
+
+
+class CfdScriptOptions(C.Structure):       # cfd_script_options
+    _fields_ = [("residual_f64", C.c_int32), ("residual_scaling", C.c_int32)]
 
 
 class CfdResiduals(C.Structure):
@@ -242,6 +247,9 @@ def load():
         "cfd_script_update": (i32, [vp, C.POINTER(CfdScriptConfig), C.POINTER(CfdScriptReport)]),
         "cfd_script_update_n": (i32, [vp, C.POINTER(CfdScriptConfig), i32,
                                       C.POINTER(CfdScriptReport)]),
+        "cfd_script_set_options": (i32, [vp, C.POINTER(CfdScriptOptions)]),
+        "cfd_script_get_options": (i32, [vp, C.POINTER(CfdScriptOptions)]),
+        "cfd_get_p_residual_f64": (i32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "cfd_tracers_enable": (i32, [vp, C.c_uint64, i32]),
         "cfd_tracers_disable": (i32, [vp]),
         "cfd_tracers_count": (i32, [vp, C.POINTER(C.c_uint64)]),

@@ -34,6 +34,30 @@ __device__ __forceinline__ void publish_max(uint32_t *set, int key, float m) {
     if (m > 0.0f) atomicMax(&set[(key & (kResSlots - 1)) * kResStride], __float_as_uint(m));
 }
 
+// The maximum over the wave of a double that is non-negative and not NaN (the
+// lanes fold with fmax from 0.0, which never takes a NaN): such a double orders
+// as its 64 bits, so the lanes exchange the two halves and compare integers.
+__device__ __forceinline__ double wave_max_pos_f64(double m) {
+    unsigned long long b = (unsigned long long)__double_as_longlong(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(b >> 32), o, 64);
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)b, o, 64);
+        const unsigned long long t = ((unsigned long long)hi << 32) | lo;
+        b = t > b ? t : b;
+    }
+    return __longlong_as_double((long long)b);
+}
+// ... and into slot `key` of a 64-bit spread set (cfd_internal.h kRes64Stride)
+__device__ __forceinline__ void publish_max_pos_f64(unsigned long long *set, int key, double m) {
+    if (m > 0.0)
+        atomicMax(&set[(size_t)(key & (kResSlots - 1)) * kRes64Stride],
+                  (unsigned long long)__double_as_longlong(m));
+}
+// the accumulators of the kernels that fold a residual as f32 or as a double
+__device__ __forceinline__ float acc_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double acc_max(double a, double b) { return fmax(a, b); }
+
 // |x| as bits: NaN and Inf compare above every finite value as unsigned integers
 __device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 // Raise a bound word (Ctl::sums_m0 / sums_rm) to this lane's maximum of

@@ -104,7 +104,19 @@ struct Ctl {
     uint32_t sums_m0, sums_rm;   // max |p'| / max |rhs| as bits & 0x7fffffff (NaN, Inf: above every finite)
     int32_t go[kMaxPasses + 1];      // go[p]: pass p of the corrector loop runs
     uint32_t err[kMaxSweeps];        // per-sweep max |p'new - p'| as f32 bits
+    // the script's double of last_p (cfd_script_options.residual_f64; solvers
+    // 2, 4 and 5): the residual of the last iteration run, whose f32 rounding
+    // is last_p.  Written by k_publish_f64 behind the solve's finalize.
+    double last_p64;
 };
+
+// The double residual's spread maxima (cfd_script_options.residual_f64): a
+// non-negative double orders as its 64 bits, so iteration k of a solve owns
+// kResSlots 64-bit words res64[(k * kResSlots + s) * kRes64Stride], one 64-byte
+// line each, raised with 64-bit atomicMax.  Zero between solves; allocated
+// when the option is switched on, released when it is switched off.
+constexpr int kRes64Stride = 8;
+constexpr size_t kRes64Words = (size_t)kMaxSweeps * kResSlots * kRes64Stride;
 
 // Scalars every kernel needs; passed by value as a kernel argument.
 struct Geom {
@@ -328,9 +340,14 @@ void launch_fill_zero(float *p, size_t n, const Ctl *ctl, int pass, hipStream_t 
 // buffer once per iteration run.  pol: sor_lex_words(iters, ny) words the
 // launcher zeroes before each launch; exitw: 4 words.  iters >= 1.
 size_t sor_lex_words(int iters, int ny);
+// res64 (both solvers below and launch_mg_final_residual): null, or the double
+// residual's slot sets -- the launch then runs the kernel's second
+// instantiation, which folds the maximum as a double, raises set k of res64
+// with it and derives the f32 it publishes as before from that double.
 hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
                           Ctl *ctl, uint32_t *pol, uint32_t *exitw, uint32_t *host_fail, int pass,
-                          int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s);
+                          int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s,
+                          unsigned long long *res64 = nullptr);
 // The script's Jacobi, omega 0.7 (cfd_jacobi_script.hip, pressure_solver 5):
 // one whole iteration per launch -- interior update, max |new - old| into
 // err_slots' set `it`, boundary copies -- ping-pong between pa / pb from
@@ -339,7 +356,13 @@ hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny
 // ny >= 3, whole domain.
 void launch_jacobi_script(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
                           Ctl *ctl, uint32_t *err_slots, int pass, int it, int tol, float p_tol,
-                          int res, hipStream_t s);
+                          int res, hipStream_t s, unsigned long long *res64 = nullptr);
+// Behind the finalize of a solve that raised res64: Ctl::last_p64 = the
+// maximum of set n_exec_last - 1 (0.0 when no iteration ran), then the sets the
+// solve can have raised are zeroed again: [z_lo, iters), or with to_n
+// [z_lo, n_exec_last).
+void launch_publish_f64(const Fields &f, unsigned long long *res64, int pass, int iters, int z_lo,
+                        int to_n, hipStream_t s);
 void launch_mg_smooth(const MgLevel &L, const float *src, float *dst, const Ctl *ctl, int pass,
                       hipStream_t s);
 // Five smoothing sweeps src -> dst in one launch (temporal blocking: one
@@ -363,7 +386,7 @@ void launch_mg_prolong_add(const MgLevel &Cl, const float *e, const MgLevel &F, 
 void launch_mg_tail(const MgLevel *dev_levels, int s_level, int coarsest, float *a0, float *b0,
                     int fast, const Ctl *ctl, int pass, hipStream_t s);
 void launch_mg_final_residual(const MgLevel &L, const float *p, uint32_t *slots, const Ctl *ctl,
-                              int pass, hipStream_t s);
+                              int pass, hipStream_t s, unsigned long long *res64 = nullptr);
 void launch_corrector(const Geom &g, const Fields &f, int pass, float dt_override,
                       hipStream_t s);
 void launch_boundary(const Geom &g, const Fields &f, hipStream_t s);
@@ -450,8 +473,10 @@ void launch_script_correct(const Geom &g, const Fields &f, const ScriptStep &k, 
 // The step's reduction block, 64-bit words: three spread maxima of doubles as
 // their bits (max |u - uOld|, max |v - vOld|, max(|u|, |v|); kResSlots slots
 // each, one 64-byte line per slot), then one line whose first f32 is the
-// running maximum of the substeps' pressure residuals.  Zeroed by the host (in
-// stream order) when a step starts, read back once when it ends.
+// running maximum of the substeps' pressure residuals and whose second 64-bit
+// word is the running maximum of their doubles (k_script_pmax64, when the
+// solves publish Ctl::last_p64).  Zeroed by the host (in stream order) when a
+// step starts, read back once when it ends.
 constexpr int kScrRedStride = 8;
 constexpr int kScrRedPmax = 3 * kResSlots * kScrRedStride;
 constexpr int kScrRedWords = kScrRedPmax + kScrRedStride;
@@ -459,6 +484,7 @@ constexpr int kScrRedWords = kScrRedPmax + kScrRedStride;
 void launch_script_begin(const Fields &f, float *u_prev, float *u_old, float *v_prev, float *v_old,
                          long nu, long nv, int extrapolate, hipStream_t s);
 void launch_script_pmax(const Fields &f, unsigned long long *red, hipStream_t s);
+void launch_script_pmax64(const Fields &f, unsigned long long *red, hipStream_t s);
 void launch_script_end(const Fields &f, float *u_prev, const float *u_old, float *v_prev,
                        const float *v_old, long nu, long nv, unsigned long long *red, hipStream_t s);
 

@@ -28,7 +28,15 @@
 // iteration's residual slots and returns at once (the red-black SOR's
 // predicate).  Every operation is a separate IEEE double operation in the
 // script's order (-ffp-contract=off); one rounding to f32 on the store.
+//
+// F64 (k_jacobi_script_f64, cfd_script_options.residual_f64): the same body
+// with the maximum kept as the script's double.  A wave raises set `it` of
+// res64 with it and publishes (float) of it into err_slots as the other
+// instantiation publishes its f32 maximum: rounding is monotone, so that is
+// the same f32, and the exit test above and the finalize read it unchanged.
 #include "cfd_device.h"
+
+#include <type_traits>
 
 namespace cfd {
 namespace {
@@ -50,20 +58,23 @@ __device__ __forceinline__ float js_relax(const SorConst &k, float c, float e, f
 __device__ __forceinline__ float js_err(float m, float nv, float old) {
     return fmaxf(m, (float)fabs((double)nv - (double)old));
 }
+__device__ __forceinline__ double js_err(double m, float nv, float old) {
+    return fmax(m, fabs((double)nv - (double)old));
+}
 
 __device__ __forceinline__ float2 js_ld(const float *__restrict__ p, long off, bool on) {
     return on ? *reinterpret_cast<const float2 *>(p + off) : make_float2(0.0f, 0.0f);
 }
 
-template <int FAST>
-__global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restrict__ pa,
-                                                          const float *__restrict__ pb,
-                                                          float *__restrict__ qa, float *__restrict__ qb,
-                                                          const float *__restrict__ rhs, int nx, int ny,
-                                                          SorConst k, Ctl *ctl, uint32_t *err_slots,
-                                                          int pass, int it, int tol, float p_tol,
-                                                          int res, int nwc, int nseg) {
-    if (pass_off(ctl, pass)) return;
+template <int FAST, int F64>
+__device__ __forceinline__ void jacobi_script_body(const float *__restrict__ pa,
+                                                   const float *__restrict__ pb,
+                                                   float *__restrict__ qa, float *__restrict__ qb,
+                                                   const float *__restrict__ rhs, int nx, int ny,
+                                                   const SorConst &k, Ctl *ctl, uint32_t *err_slots,
+                                                   int pass, int it, int tol, float p_tol, int res,
+                                                   int nwc, int nseg, unsigned long long *res64) {
+    typedef typename std::conditional<F64 != 0, double, float>::type acc_t;
     // :836, decided here: the previous iteration was the solve's last
     if (tol && it > 0 &&
         read_max(err_slots + (size_t)(it - 1) * kResSlots * kResStride, ctl->err[it - 1]) < p_tol)
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restric
     const int r0 = 1 + seg * kJsRows;
     const int r1 = min(r0 + kJsRows, ny - 1);          // interior rows [r0, r1), r0 < r1 <= ny-1
     float2 dn = js_ld(src, (long)(r0 - 1) * nx + i0, rd), a = js_ld(src, (long)r0 * nx + i0, rd);
-    float m = 0.0f;
+    acc_t m = 0;
 #pragma unroll
     for (int t = 0; t < kJsRows; ++t) {
         const int j = r0 + t;
@@ -95,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restric
         // every lane shifts (halo and out-of-domain lanes hold zeros)
         const float w_of_x = from_left(a.y), e_of_y = from_right(a.x);
         float2 o = a;
-        float mm = 0.0f;
+        acc_t mm = 0;
         if (i0 >= 1) {
             o.x = js_relax<FAST>(k, a.x, a.y, w_of_x, up.x, dn.x, rh.x);
             mm = js_err(mm, o.x, a.x);
@@ -107,7 +118,7 @@ __global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restric
         if (i0 == 0) o.x = o.y;            // :833 P(0,j) = P(1,j)
         if (i0 + 1 == nx - 1) o.y = 0.0f;  // :834 P(nx-1,j) = 0
         if (out) {
-            m = fmaxf(m, mm);
+            m = acc_max(m, mm);
             *reinterpret_cast<float2 *>(dst + (long)j * nx + i0) = o;
             if (j == 1) *reinterpret_cast<float2 *>(dst + i0) = o;                               // :829 row 0
             if (j == ny - 2) *reinterpret_cast<float2 *>(dst + (long)(ny - 1) * nx + i0) = o;   // :830 row ny-1
@@ -116,19 +127,58 @@ __global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restric
         a = up;
     }
     if (!res) return;
-    m = wave_max(m);
-    if (lane == 0) publish_max(err_slots + (size_t)it * kResSlots * kResStride, bid * (kBlock / 64) + wave, m);
+    if (F64) {
+        const double md = wave_max_pos_f64((double)m);
+        if (lane == 0) {
+            const int key = bid * (kBlock / 64) + wave;
+            publish_max_pos_f64(res64 + (size_t)it * kResSlots * kRes64Stride, key, md);
+            publish_max(err_slots + (size_t)it * kResSlots * kResStride, key, (float)md);
+        }
+        return;
+    }
+    const float mf = wave_max((float)m);
+    if (lane == 0) publish_max(err_slots + (size_t)it * kResSlots * kResStride, bid * (kBlock / 64) + wave, mf);
+}
+
+template <int FAST>
+__global__ __launch_bounds__(kBlock) void k_jacobi_script(const float *__restrict__ pa,
+                                                          const float *__restrict__ pb,
+                                                          float *__restrict__ qa, float *__restrict__ qb,
+                                                          const float *__restrict__ rhs, int nx, int ny,
+                                                          SorConst k, Ctl *ctl, uint32_t *err_slots,
+                                                          int pass, int it, int tol, float p_tol,
+                                                          int res, int nwc, int nseg) {
+    if (pass_off(ctl, pass)) return;
+    jacobi_script_body<FAST, 0>(pa, pb, qa, qb, rhs, nx, ny, k, ctl, err_slots, pass, it, tol, p_tol, res,
+                                nwc, nseg, nullptr);
+}
+
+template <int FAST>
+__global__ __launch_bounds__(kBlock) void k_jacobi_script_f64(
+    const float *__restrict__ pa, const float *__restrict__ pb, float *__restrict__ qa,
+    float *__restrict__ qb, const float *__restrict__ rhs, int nx, int ny, SorConst k, Ctl *ctl,
+    uint32_t *err_slots, int pass, int it, int tol, float p_tol, int res, int nwc, int nseg,
+    unsigned long long *res64) {
+    if (pass_off(ctl, pass)) return;
+    jacobi_script_body<FAST, 1>(pa, pb, qa, qb, rhs, nx, ny, k, ctl, err_slots, pass, it, tol, p_tol, res,
+                                nwc, nseg, res64);
 }
 
 }  // namespace
 
 void launch_jacobi_script(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
                           Ctl *ctl, uint32_t *err_slots, int pass, int it, int tol, float p_tol,
-                          int res, hipStream_t s) {
+                          int res, hipStream_t s, unsigned long long *res64) {
     const int nwc = cdiv(nx / 2, 62);
     const int nseg = cdiv(ny - 2, kJsRows);
     const dim3 grid(nwc * cdiv(nseg, kBlock / 64));
-    if (k.fast)
+    if (res64 && k.fast)
+        hipLaunchKernelGGL(k_jacobi_script_f64<1>, grid, dim3(kBlock), 0, s, pa, pb, pa, pb, rhs, nx, ny,
+                           k, ctl, err_slots, pass, it, tol, p_tol, res, nwc, nseg, res64);
+    else if (res64)
+        hipLaunchKernelGGL(k_jacobi_script_f64<0>, grid, dim3(kBlock), 0, s, pa, pb, pa, pb, rhs, nx, ny,
+                           k, ctl, err_slots, pass, it, tol, p_tol, res, nwc, nseg, res64);
+    else if (k.fast)
         hipLaunchKernelGGL(k_jacobi_script<1>, grid, dim3(kBlock), 0, s, pa, pb, pa, pb, rhs, nx, ny, k,
                            ctl, err_slots, pass, it, tol, p_tol, res, nwc, nseg);
     else

@@ -239,6 +239,13 @@ struct cfd_model {
     // --------------------- the other solvers (cfd_model_solvers.hip)
     uint32_t *lex_pol = nullptr, *lex_exit = nullptr;   // script-order SOR's tickets
     size_t lex_words = 0;
+    // cfd_script_options: solves 2, 4 and 5 also publish the script's double
+    // residual (Ctl::last_p64) through res64, the slot sets their second
+    // instantiations raise (cfd_internal.h kRes64Words; allocated while the
+    // option is set).  p64_valid: the last solve enqueued published one.
+    cfd_script_options sopt{};
+    unsigned long long *res64 = nullptr;
+    bool p64_valid = false;
     // multigrid hierarchy (cfd_solvers.hip), built on the first multigrid solve
     std::vector<cfd::MgLevel> mg;     // level table; level 0's a/b are the p' buffers of the solve
     cfd::MgLevel *mg_dev = nullptr;   // device copy for k_mg_tail
@@ -324,6 +331,7 @@ struct cfd_model {
     int32_t su_substeps = 5;      // let substepCount
     uint64_t su_steps = 0;        // simulationStepCount
     double su_inlet = 0.0;        // currentInletVelocity
+    double su_pmax64 = 0.0;       // maxPressureResidual of the last update whose solves published doubles
 
     // ============================================================ methods
     bool sharded() const { return n_ranks > 1; }
@@ -384,6 +392,9 @@ struct cfd_model {
     int enqueue_sor_sharded_deep(const cfd::SorConst &k, int pass, hipEvent_t e0);
     int enqueue_sor_lex(int pass);
     int enqueue_jacobi_script(int pass);
+    // the double residual's slot sets when this model's solves publish it, else null
+    unsigned long long *res64_on() const { return sopt.residual_f64 && !sharded() ? res64 : nullptr; }
+    int clear_res64();
     void mg_rows(int l, int r, int *j0o, int *j1o) const;
     int mg_partition_levels(const std::vector<std::pair<int, int>> &dims, int tail) const;
     int mg_build();

@@ -395,6 +395,9 @@ int cfd_set_state(cfd_model *m, const cfd_state *st) {
     rc = m->clear_abort_words();
     if (rc) return rc;
     HIP_TRY(hipMemcpy(m->f.ctl, &c, offsetof(Ctl, go), hipMemcpyHostToDevice));
+    // a new state: no solve has published its double residual
+    HIP_TRY(hipMemset(&m->f.ctl->last_p64, 0, 8));
+    m->p64_valid = false;
     *(volatile uint32_t *)m->h_nonfinite = 0u;
     m->host_cur = c.cur;
     // ghosts of the injected slab
@@ -403,6 +406,47 @@ int cfd_set_state(cfd_model *m, const cfd_state *st) {
     rc = m->exchange_pp(c.cur, m->g.hg);
     if (rc) return rc;
     return m->sync();
+}
+
+int cfd_script_set_options(cfd_model *m, const cfd_script_options *o) {
+    if (!m || !o) return fail(CFD_EINVAL, "null argument");
+    if (m->sharded()) return fail(CFD_EINVAL, "script options need a single-domain model");
+    if ((o->residual_f64 != 0 && o->residual_f64 != 1) ||
+        (o->residual_scaling != 0 && o->residual_scaling != 1))
+        return fail(CFD_EINVAL, "script options take 0 or 1");
+    if (int rc = m->sync()) return rc;
+    m->drop_graph();   // the solve's kernels follow the option
+    cfd_script_options n = *o;
+    if (n.residual_scaling) n.residual_f64 = 1;
+    if (n.residual_f64 && !m->res64) {
+        HIP_TRY(hipMalloc((void **)&m->res64, kRes64Words * 8));
+        if (int rc = m->clear_res64()) return rc;
+    }
+    if (!n.residual_f64) {
+        m->p64_valid = false;
+        if (m->res64) HIP_TRY(hipFree(m->res64));   // the device is idle (sync above)
+        m->res64 = nullptr;
+    }
+    m->sopt = n;
+    return 0;
+}
+
+int cfd_script_get_options(const cfd_model *m, cfd_script_options *o) {
+    if (!m || !o) return fail(CFD_EINVAL, "null argument");
+    *o = m->sopt;
+    return 0;
+}
+
+int cfd_get_p_residual_f64(cfd_model *m, double *last, double *step_max) {
+    if (!m) return fail(CFD_EINVAL, "null model");
+    if (!m->sopt.residual_f64) return fail(CFD_ESTATE, "residual_f64 is off (cfd_script_set_options)");
+    if (!m->p64_valid)
+        return fail(CFD_ESTATE, "no solve has published a double residual: none has run since the option "
+                                "was set or the state was replaced, or the last one was solver 0 or 1");
+    if (int rc = m->sync()) return rc;
+    if (last) HIP_TRY(hipMemcpy(last, &m->f.ctl->last_p64, 8, hipMemcpyDeviceToHost));
+    if (step_max) *step_max = m->su_pmax64;
+    return 0;
 }
 
 int cfd_get_masks(cfd_model *m, uint8_t *mask_u, uint8_t *mask_v) {

@@ -507,7 +507,8 @@ void cfd_model::destroy() {
                       (void *)us_all, (void *)vs_all, (void *)p, (void *)rhs,
                       (void *)pp_all[0], (void *)pp_all[1], (void *)mask_u, (void *)mask_v,
                       (void *)obs, (void *)ctl, (void *)slots, (void *)vis_buf,
-                      (void *)mg_pool, (void *)mg_dev, (void *)lex_pol, (void *)lex_exit})
+                      (void *)mg_pool, (void *)mg_dev, (void *)lex_pol, (void *)lex_exit,
+                      (void *)res64})
         if (ptr) (void)hipFree(ptr);
     if (h_nonfinite) (void)hipHostFree(h_nonfinite);
     if (ck_pool) (void)hipFree(ck_pool);

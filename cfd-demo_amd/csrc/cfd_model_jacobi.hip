@@ -106,6 +106,10 @@ int cfd_model::launch_persist(int pass, int par0, int nblk, int lo, int hi, int 
 }
 
 int cfd_model::enqueue_solve(int pass) {
+    // solvers 2, 4 and 5 publish the script's double when the option is on
+    p64_valid = res64_on() && (params.pressure_solver == CFD_SOLVER_MULTIGRID ||
+                               params.pressure_solver == CFD_SOLVER_SOR_LEX ||
+                               params.pressure_solver == CFD_SOLVER_JACOBI_SCRIPT);
     if (params.pressure_solver == CFD_SOLVER_SOR) return enqueue_sor(pass);
     if (params.pressure_solver == CFD_SOLVER_MULTIGRID) return enqueue_mg(pass);
     if (params.pressure_solver == CFD_SOLVER_SOR_LEX) return enqueue_sor_lex(pass);

@@ -72,6 +72,9 @@ int cfd_model::su_update(const cfd_script_config *c, cfd_script_report *out) {
     if (int rc = script_check(this, &s)) return rc;
     HIP_TRY(hipSetDevice(device));
     const long nu = ((long)g.nx + 1) * g.ny, nv = (long)g.nx * ((long)g.ny + 1);
+    // the substeps' solves publish the script's double (script_check admits
+    // solvers 2, 4 and 5 only): every decision below is then taken from it
+    const bool p64 = res64_on() != nullptr;
     // From the begin pass on u and v are no longer the step's start: a failure
     // before the step's end (a solve that timed out, a HIP error) leaves them
     // extrapolated or part-way through the substeps, so the path then refuses
@@ -82,7 +85,10 @@ int cfd_model::su_update(const cfd_script_config *c, cfd_script_report *out) {
         HIP_TRY(hipGetLastError());
         for (int sub = 0; sub < nsub; ++sub) {   // :288-293
             if (int rc = script_substep(&s)) return rc;
-            launch_script_pmax(f, su_red, stream);
+            if (p64)
+                launch_script_pmax64(f, su_red, stream);
+            else
+                launch_script_pmax(f, su_red, stream);
             HIP_TRY(hipGetLastError());
         }
         launch_script_end(f, su_uprev, su_uold, su_vprev, su_vold, nu, nv, su_red, stream);
@@ -104,7 +110,10 @@ int cfd_model::su_update(const cfd_script_config *c, cfd_script_report *out) {
     }
     float pmax_f;
     std::memcpy(&pmax_f, &su_h[kScrRedPmax], 4);
-    const double res_u = mx[0], res_v = mx[1], max_vel = mx[2], res_p = (double)pmax_f;
+    double pmax_d;
+    std::memcpy(&pmax_d, &su_h[kScrRedPmax + 1], 8);
+    const double res_u = mx[0], res_v = mx[1], max_vel = mx[2], res_p = p64 ? pmax_d : (double)pmax_f;
+    if (p64) su_pmax64 = pmax_d;
 
     ++su_steps;   // :307
     // :310-317
@@ -129,9 +138,16 @@ int cfd_model::su_update(const cfd_script_config *c, cfd_script_report *out) {
         dt_cfl = 0.5 * (dx < dy ? dx : dy) / max_vel;
         if (c->dt_user < dt_cfl) dt_cfl = c->dt_user;   // Math.min, neither is NaN
     }
+    // :337-350: residualScalingEnabled scales dt_cfl by the pressure residual
+    double new_dt = dt_cfl;
+    if (sopt.residual_scaling) {
+        const double pressure_tol = 1e-3;
+        double dt_pressure = dt_cfl;
+        if (res_p > pressure_tol) dt_pressure = dt_cfl * (pressure_tol / (res_p + 1e-10));
+        new_dt = dt_pressure < dt_cfl ? dt_pressure : dt_cfl;   // Math.min, neither is NaN
+    }
     // :352-357
     const double previous = su_dt;
-    double new_dt = dt_cfl;
     if (new_dt > previous) {
         const double lim = previous * 1.1;
         if (lim < new_dt) new_dt = lim;

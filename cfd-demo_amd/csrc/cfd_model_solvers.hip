@@ -207,6 +207,7 @@ int cfd_model::enqueue_sor_lex(int pass) {
     if (sharded()) return fail(CFD_EINVAL, "pressure_solver 4 (script-order SOR) runs on one domain only");
     hipEvent_t e0;
     begin_solve_timing(pass, &e0);
+    unsigned long long *const r64 = res64_on();
     int launches = 0;
     if (iters < 1) {
         // p' = 0 (index.html:743) in whichever buffer is current
@@ -225,10 +226,12 @@ int cfd_model::enqueue_sor_lex(int pass) {
         if (!lex_exit) HIP_TRY(hipMalloc((void **)&lex_exit, 16));
         HIP_TRY(launch_sor_lex(f.pp[0], f.pp[1], f.rhs, g.nx, g.ny, sor_consts(), f.ctl, lex_pol,
                                lex_exit, f.host_nonfinite ? f.host_nonfinite + 2 : nullptr, pass,
-                               iters, g.tol_enabled, g.p_tol, g.n_cu, &launches, stream));
+                               iters, g.tol_enabled, g.p_tol, g.n_cu, &launches, stream, r64));
     }
     end_solve_timing(e0, (uint64_t)iters, (uint64_t)launches);
     launch_finalize_solve(g, f, pass, iters, pass >= 1 ? 1 : 0, iters, stream);
+    // every iteration publishes, those that ran past an exit included
+    if (r64) launch_publish_f64(f, r64, pass, iters, 0, 0, stream);
     if (!g.tol_enabled) host_cur = (host_cur + iters) & 1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -252,11 +255,17 @@ int cfd_model::enqueue_jacobi_script(int pass) {
         launches = 2;
     }
     const SorConst k = sor_consts();
+    unsigned long long *const r64 = res64_on();
     for (int it = 0; it < iters; ++it)
         launch_jacobi_script(f.pp[0], f.pp[1], f.rhs, g.nx, g.ny, k, f.ctl, f.err_slots, pass, it,
-                             g.tol_enabled, g.p_tol, g.tol_enabled || it == iters - 1, stream);
+                             g.tol_enabled, g.p_tol, g.tol_enabled || it == iters - 1, stream, r64);
     end_solve_timing(e0, (uint64_t)iters, (uint64_t)launches);
     launch_finalize_solve(g, f, pass, iters, pass >= 1 ? 1 : 0, iters, stream);
+    // with the tolerance on every iteration up to the exit publishes (later
+    // launches return first); a fixed count publishes its last iteration only
+    if (r64)
+        launch_publish_f64(f, r64, pass, iters, g.tol_enabled ? 0 : std::max(iters - 1, 0),
+                           g.tol_enabled ? 1 : 0, stream);
     if (!g.tol_enabled) host_cur = (host_cur + iters) & 1;
     HIP_TRY(hipGetLastError());
     return 0;
@@ -664,7 +673,8 @@ int cfd_model::enqueue_mg(int pass, float *residual_out) {
             launches += 1;
         }
     }
-    launch_mg_final_residual(L0, L0.a, f.err_slots, f.ctl, pass, stream);
+    unsigned long long *const r64 = res64_on();
+    launch_mg_final_residual(L0, L0.a, f.err_slots, f.ctl, pass, stream, r64);
     if (sharded()) {
         // the slab's rows and its hg ghost rows (inside the grid) of the
         // whole-grid solution: the deep ghosts are exact afterwards
@@ -675,6 +685,7 @@ int cfd_model::enqueue_mg(int pass, float *residual_out) {
     }
     end_solve_timing(e0, 1, (uint64_t)launches + 1);
     launch_finalize_solve(g, f, pass, 1, pass >= 1 ? 1 : 0, 0, stream, 1);
+    if (r64) launch_publish_f64(f, r64, pass, 1, 0, 0, stream);
     HIP_TRY(hipGetLastError());
     if (residual_out) {
         float r = 0.f;
@@ -683,5 +694,12 @@ int cfd_model::enqueue_mg(int pass, float *residual_out) {
         if (rc) return rc;
         *residual_out = r;
     }
+    return 0;
+}
+
+// the double residual's slot sets are zero between solves; a solve that timed
+// out may have left some behind
+int cfd_model::clear_res64() {
+    if (res64) HIP_TRY(hipMemset(res64, 0, kRes64Words * 8));
     return 0;
 }

@@ -282,6 +282,7 @@ int cfd_model::persist_timeout_check(bool at_sync) {
         HIP_TRY(hipStreamSynchronize(stream));
         *(volatile uint32_t *)(h_nonfinite + 2) = 0u;
         clear_abort_words();
+        clear_res64();
         return fail(CFD_ETIMEOUT, "script-order SOR solve timed out waiting for a workgroup; "
                                   "its result is invalid until cfd_set_state");
     }
@@ -367,6 +368,8 @@ int cfd_model::recover() {
     // have left some behind
     HIP_TRY(hipMemset(f.err_slots, 0, (size_t)kMaxSweeps * kResSlots * kResStride * 4));
     int rc = clear_abort_words();
+    if (rc) return rc;
+    rc = clear_res64();
     if (rc) return rc;
     *(volatile uint32_t *)h_nonfinite = 0u;
     host_cur = ck_host_cur;

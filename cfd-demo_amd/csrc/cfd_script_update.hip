@@ -5,6 +5,8 @@
 //                             uOld written;
 //   k_script_pmax   :290-292  the running maximum of the substeps' pressure
 //                             residuals, one word folded after each solve;
+//   k_script_pmax64           the same on the doubles the solves publish under
+//                             cfd_script_options.residual_f64, in its place;
 //   k_script_end    :296-305, :1323-1333, :361-362  max |u - uOld|,
 //                             max |v - vOld|, max(|u|, |v|) and uPrev = u,
 //                             vPrev = v in one pass over u, v, uOld, vOld.
@@ -113,6 +115,14 @@ __global__ void k_script_pmax(const Ctl *__restrict__ ctl, unsigned long long *_
     if (r > *pm) *pm = r;
 }
 
+// its sibling for solves that publish the script's double (Ctl::last_p64): the
+// same comparison on doubles, into the line's second 64-bit word
+__global__ void k_script_pmax64(const Ctl *__restrict__ ctl, unsigned long long *__restrict__ red) {
+    double *pm = reinterpret_cast<double *>(red + kScrRedPmax + 1);
+    const double r = ctl->last_p64;
+    if (r > *pm) *pm = r;
+}
+
 }  // namespace
 
 void launch_script_begin(const Fields &f, float *u_prev, float *u_old, float *v_prev, float *v_old,
@@ -131,6 +141,10 @@ void launch_script_end(const Fields &f, float *u_prev, const float *u_old, float
 
 void launch_script_pmax(const Fields &f, unsigned long long *red, hipStream_t s) {
     hipLaunchKernelGGL(k_script_pmax, dim3(1), dim3(1), 0, s, f.ctl, red);
+}
+
+void launch_script_pmax64(const Fields &f, unsigned long long *red, hipStream_t s) {
+    hipLaunchKernelGGL(k_script_pmax64, dim3(1), dim3(1), 0, s, f.ctl, red);
 }
 
 }  // namespace cfd

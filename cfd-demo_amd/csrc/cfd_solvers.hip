@@ -752,6 +752,64 @@ __global__ __launch_bounds__(kBlock) void k_mg_final_residual(MgLevel L, const f
     }
 }
 
+// The same kernel for cfd_script_options.residual_f64, written out beside it
+// so that the one above stays the code it was: the maximum stays the script's
+// double, the block raises set 0 of res64 with it and publishes (float) of it
+// into `slots` -- the f32 the kernel above publishes, rounding being monotone.
+template <int FAST>
+__global__ __launch_bounds__(kBlock) void k_mg_final_residual_f64(MgLevel L, const float *p,
+                                                                  uint32_t *slots, const Ctl *ctl,
+                                                                  int pass, int nbx, int rows,
+                                                                  unsigned long long *res64) {
+    if (pass_off(ctl, pass)) return;
+    __shared__ double wmax[kBlock / 64];
+    const int i = ((int)blockIdx.x % nbx) * kBlock + (int)threadIdx.x;
+    const int jb = L.lo + ((int)blockIdx.x / nbx) * rows;   // rows [lo, hi)
+    const int nx = L.nx;
+    double m = 0.0;
+    if (i >= 1 && i <= nx - 2) {
+        const int j1 = min(jb + rows, min(L.hi, L.ny - 1));
+        for (int j = max(jb, 1); j < j1; ++j) {
+            const long idx = (long)j * nx + i;
+            const double r = ddiv<FAST>((double)p[idx + 1] + (double)p[idx - 1], L.dx2, L.r_dx2) +
+                             ddiv<FAST>((double)p[idx + nx] + (double)p[idx - nx], L.dy2, L.r_dy2) -
+                             L.denom * (double)p[idx] - (double)L.rhs[idx];
+            m = fmax(m, fabs(r));   // a NaN is never taken
+        }
+    }
+    m = wave_max_pos_f64(m);
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double b = wmax[0];
+        for (int w = 1; w < kBlock / 64; ++w) b = fmax(b, wmax[w]);
+        publish_max_pos_f64(res64, (int)blockIdx.x, b);
+        publish_max(slots, (int)blockIdx.x, (float)b);
+    }
+}
+
+// Behind k_finalize_solve of a solve whose kernels raised res64: the finalize
+// left the iterations run in Ctl::n_exec_last, and the residual it put into
+// last_p is the f32 of that iteration's set.  Fold the set into Ctl::last_p64
+// (0.0 when no iteration ran), then zero the sets the solve can have raised:
+// [z_lo, iters), or [z_lo, n_exec_last) with to_n (a solve whose launches past
+// the exit return before they publish).
+__global__ __launch_bounds__(kBlock) void k_publish_f64(Ctl *ctl, unsigned long long *res64, int pass,
+                                                        int iters, int z_lo, int to_n) {
+    if (pass_off(ctl, pass)) return;   // the solve did not run: last_p stayed too
+    const int n = (int)ctl->n_exec_last;
+    if (threadIdx.x < 64) {
+        const int lane = (int)threadIdx.x;
+        unsigned long long b = 0ull;
+        if (n > 0 && lane < kResSlots) b = res64[((size_t)(n - 1) * kResSlots + lane) * kRes64Stride];
+        const double v = wave_max_pos_f64(__longlong_as_double((long long)b));
+        if (lane == 0) ctl->last_p64 = v;
+    }
+    __syncthreads();
+    const long z0 = (long)z_lo * kResSlots, z1 = (long)(to_n ? min(n, iters) : iters) * kResSlots;
+    for (long k = z0 + threadIdx.x; k < z1; k += blockDim.x) res64[k * kRes64Stride] = 0ull;
+}
+
 // interior rows per k_sor_march segment: 32 where the slab has
 // them (4096^2, 200 iterations: 9.02 ms; 8 rows 9.60, 16 rows 9.94, 64 rows
 // 13.45), else 16 (the minimum: sor_fused_ok)
@@ -964,16 +1022,27 @@ void launch_mg_tail(const MgLevel *dev_levels, int s_level, int coarsest, float 
 }
 
 void launch_mg_final_residual(const MgLevel &L, const float *p, uint32_t *slots, const Ctl *ctl,
-                              int pass, hipStream_t s) {
+                              int pass, hipStream_t s, unsigned long long *res64) {
     const int nbx = cdiv(L.nx, kBlock);
     const int rows = 32;
     const dim3 grid(nbx * std::max(1, cdiv(L.hi - L.lo, rows)));
-    if (L.fast)
+    if (res64 && L.fast)
+        hipLaunchKernelGGL(k_mg_final_residual_f64<1>, grid, dim3(kBlock), 0, s, L, p, slots, ctl, pass,
+                           nbx, rows, res64);
+    else if (res64)
+        hipLaunchKernelGGL(k_mg_final_residual_f64<0>, grid, dim3(kBlock), 0, s, L, p, slots, ctl, pass,
+                           nbx, rows, res64);
+    else if (L.fast)
         hipLaunchKernelGGL(k_mg_final_residual<1>, grid, dim3(kBlock), 0, s, L, p, slots, ctl, pass,
                            nbx, rows);
     else
         hipLaunchKernelGGL(k_mg_final_residual<0>, grid, dim3(kBlock), 0, s, L, p, slots, ctl, pass,
                            nbx, rows);
+}
+
+void launch_publish_f64(const Fields &f, unsigned long long *res64, int pass, int iters, int z_lo,
+                        int to_n, hipStream_t s) {
+    hipLaunchKernelGGL(k_publish_f64, dim3(1), dim3(kBlock), 0, s, f.ctl, res64, pass, iters, z_lo, to_n);
 }
 
 }  // namespace cfd

@@ -48,7 +48,15 @@
 // test off; it reads the count from the exit word on the device and returns
 // at once when no later iteration had started (no early exit, or an exit at
 // the last iteration).
+//
+// F64 (k_sor_lex_f64, cfd_script_options.residual_f64): the same body with the
+// band's maximum kept as the script's double; it raises set k of res64 and
+// folds (float) of it into ctl->err[k] as the other instantiation folds its f32
+// maximum -- the same f32, rounding being monotone -- so the exit test, the
+// waits and the replay are unchanged.
 #include "cfd_device.h"
+
+#include <type_traits>
 
 #include <cstdlib>
 
@@ -70,13 +78,13 @@ __device__ __forceinline__ void lex_store(float *p, float v) {
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int FAST>
-__global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const float *__restrict__ rhs,
-                                                int nx, int ny, SorConst kc, Ctl *ctl, uint32_t *pol,
-                                                uint32_t *exitw, uint32_t *host_fail, int pass,
-                                                int iters, int B, int tol, float p_tol, int replay,
-                                                uint32_t deadline) {
-    if (pass_off(ctl, pass)) return;
+template <int FAST, int F64>
+__device__ __forceinline__ void sor_lex_body(float *pa, float *pb, const float *__restrict__ rhs, int nx,
+                                             int ny, const SorConst &kc, Ctl *ctl, uint32_t *pol,
+                                             uint32_t *exitw, uint32_t *host_fail, int pass, int iters,
+                                             int B, int tol, float p_tol, int replay, uint32_t deadline,
+                                             unsigned long long *res64) {
+    typedef typename std::conditional<F64 != 0, double, float>::type acc_t;
     const int lane = (int)threadIdx.x;
     int n_it = iters;
     if (replay) {
@@ -120,7 +128,7 @@ __global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const floa
         const bool s_ld = b > 0 || old;
         float nv_prev = 0.0f;   // this row's new value of the previous column
         float pe_prev = 0.0f;   // old value of this step's own cell (last step's east)
-        float m = 0.0f;
+        acc_t m = 0;
         int seenA = 0, seenB = 0, seenC = 0;
         int status = 0;         // 1: an exit below this iteration, 2: timeout
         for (int c = 0; c < NC; ++c) {
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const floa
                 const float nv = (float)((1.0 - omega) * p_old + omega * p_update);
                 pe_prev = pe[t];
                 if (active) {
-                    m = fmaxf(m, (float)fabs((double)nv - p_old));
+                    m = acc_max(m, (acc_t)fabs((double)nv - p_old));
                     nv_prev = nv;
                     float *d = dst + row + i;
                     lex_store(d, nv);
@@ -229,10 +237,17 @@ __global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const floa
         // the iteration's max |new - old| (index.html:757-758, NaN ignored as
         // there), folded by the solve's finalize; with the tolerance on, the
         // band that completes the iteration tests it
-        m = wave_max(valid ? m : 0.0f);
+        float mf;
+        if (F64) {
+            const double md = wave_max_pos_f64(valid ? (double)m : 0.0);
+            if (lane == 0) publish_max_pos_f64(res64 + (size_t)k * kResSlots * kRes64Stride, b, md);
+            mf = (float)md;
+        } else {
+            mf = wave_max(valid ? (float)m : 0.0f);
+        }
         if (lane == 0) {
-            if (m > 0.0f)
-                __hip_atomic_fetch_max(&ctl->err[k], __float_as_uint(m), __ATOMIC_RELAXED,
+            if (mf > 0.0f)
+                __hip_atomic_fetch_max(&ctl->err[k], __float_as_uint(mf), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
             if (tol) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -246,6 +261,28 @@ __global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const floa
     }
 }
 
+template <int FAST>
+__global__ __launch_bounds__(64) void k_sor_lex(float *pa, float *pb, const float *__restrict__ rhs,
+                                                int nx, int ny, SorConst kc, Ctl *ctl, uint32_t *pol,
+                                                uint32_t *exitw, uint32_t *host_fail, int pass,
+                                                int iters, int B, int tol, float p_tol, int replay,
+                                                uint32_t deadline) {
+    if (pass_off(ctl, pass)) return;
+    sor_lex_body<FAST, 0>(pa, pb, rhs, nx, ny, kc, ctl, pol, exitw, host_fail, pass, iters, B, tol, p_tol,
+                          replay, deadline, nullptr);
+}
+
+template <int FAST>
+__global__ __launch_bounds__(64) void k_sor_lex_f64(float *pa, float *pb, const float *__restrict__ rhs,
+                                                    int nx, int ny, SorConst kc, Ctl *ctl, uint32_t *pol,
+                                                    uint32_t *exitw, uint32_t *host_fail, int pass,
+                                                    int iters, int B, int tol, float p_tol, int replay,
+                                                    uint32_t deadline, unsigned long long *res64) {
+    if (pass_off(ctl, pass)) return;
+    sor_lex_body<FAST, 1>(pa, pb, rhs, nx, ny, kc, ctl, pol, exitw, host_fail, pass, iters, B, tol, p_tol,
+                          replay, deadline, res64);
+}
+
 }  // namespace
 
 size_t sor_lex_words(int iters, int ny) {
@@ -256,7 +293,8 @@ size_t sor_lex_words(int iters, int ny) {
 
 hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny, const SorConst &k,
                           Ctl *ctl, uint32_t *pol, uint32_t *exitw, uint32_t *host_fail, int pass,
-                          int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s) {
+                          int iters, int tol, float p_tol, int n_cu, int *launches, hipStream_t s,
+                          unsigned long long *res64) {
     const int B = cdiv(ny - 2, 64);
     const size_t bytes = sor_lex_words(iters, ny) * 4;
     const int ntasks = iters * B;
@@ -276,7 +314,15 @@ hipError_t launch_sor_lex(float *pa, float *pb, const float *rhs, int nx, int ny
     for (int replay = 0; replay <= (tol ? 1 : 0); ++replay) {
         hipError_t e = hipMemsetAsync(pol, 0, bytes, s);
         if (e != hipSuccess) return e;
-        if (k.fast)
+        if (res64 && k.fast)
+            hipLaunchKernelGGL(k_sor_lex_f64<1>, dim3(wgs), dim3(64), 0, s, pa, pb, rhs, nx, ny, k, ctl,
+                               pol, exitw, host_fail, pass, iters, B, tol, p_tol, replay, deadline,
+                               res64);
+        else if (res64)
+            hipLaunchKernelGGL(k_sor_lex_f64<0>, dim3(wgs), dim3(64), 0, s, pa, pb, rhs, nx, ny, k, ctl,
+                               pol, exitw, host_fail, pass, iters, B, tol, p_tol, replay, deadline,
+                               res64);
+        else if (k.fast)
             hipLaunchKernelGGL(k_sor_lex<1>, dim3(wgs), dim3(64), 0, s, pa, pb, rhs, nx, ny, k, ctl,
                                pol, exitw, host_fail, pass, iters, B, tol, p_tol, replay, deadline);
         else

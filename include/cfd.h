@@ -524,8 +524,11 @@ int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s);
  * 1e-4, or across an integer boundary of substepCount * errorNorm / 1e-3 (the
  * sliver note of CFD_SOLVER_SOR_LEX above, one level up); no committed fixture
  * (tests/golden/js_update_*.npz, the script's own numbers under node) is in
- * it.  residualScalingEnabled (off on the page) is not implemented: it scales
- * dt by the double residual.
+ * it.  cfd_script_set_options (below) lifts that caveat: with residual_f64 the
+ * solves publish the script's own double, errorNorm, the substep rule,
+ * residual_p and the dt rule are taken from it, and the update's decisions are
+ * the script's with no such sliver.  residual_scaling adds the page's
+ * residualScalingEnabled branch (:338-348) on that double.
  * State: uPrev, vPrev, uOld, vOld on the device and the script's dt,
  * substepCount, simulationStepCount and currentInletVelocity on the host, all
  * allocated by the first cfd_script_begin.  simulation_step, dt and the u / v
@@ -574,6 +577,47 @@ int cfd_script_update(cfd_model *m, const cfd_script_config *c, cfd_script_repor
 /* n updates (the loop, so that a binding crosses the ABI once); out_n: n
  * records or NULL.  Stops at the first failing update. */
 int cfd_script_update_n(cfd_model *m, const cfd_script_config *c, int n, cfd_script_report *out_n);
+
+/* ---- the script's double pressure residual and residualScalingEnabled ----
+ * residual_f64: solves 2, 4 and 5 (CFD_SOLVER_MULTIGRID, CFD_SOLVER_SOR_LEX,
+ * CFD_SOLVER_JACOBI_SCRIPT) run a second instantiation of their residual kernel
+ * that folds the maximum as the script's double -- max |new - old| of :757 and
+ * :817, max |A p' - rhs| of :784-794, NaN ignored as `>` ignores it -- and
+ * publish the double of the last iteration run next to last_p_residual, whose
+ * value is its f32 rounding.  The exit test stays (float)maxError < p_tol with
+ * the float tolerance (rounding is monotone: the f32 of the double maximum is
+ * the maximum of the f32s), so p', last_p_residual, the iterations run and
+ * jacobi_sweeps_total are the same bits with the option on or off; the
+ * solve-level sliver of CFD_SOLVER_SOR_LEX above (the script compares the
+ * double with the double 1e-4 or 1e-6) stays.  cfd_pressure_solve,
+ * cfd_piso_step, cfd_script_piso_step and cfd_update publish through the same
+ * solve.  With jacobi_iters 0 the double is 0.0; solvers 0 and 1 publish none.
+ * cfd_script_update then keeps the running maximum of the substeps' doubles on
+ * the device (k_script_pmax64, in k_script_pmax's place; the step's one
+ * read-back carries it) and takes errorNorm, the substep rule, residual_p of
+ * the report and the dt rule from it: the script's own numbers, with no
+ * update-level caveat.
+ * residual_scaling (implies residual_f64; setting it reads back residual_f64 1):
+ * the host adds :338-348 in C double -- dt_pressure = dt_cfl; if maxP > 1e-3,
+ * dt_pressure = dt_cfl * (1e-3 / (maxP + 1e-10)); newDt = min(dt_cfl,
+ * dt_pressure) -- before the unchanged 1.1 limit.  An infinite residual gives
+ * dt_next 0, which the dt_next <= 0 rule above reports as CFD_ENONFINITE.
+ * Both are 0 at creation and persist across cfd_script_begin (initSimulation
+ * does not touch the checkbox).  cfd_script_set_options synchronises and drops
+ * a captured step graph; CFD_EINVAL on a sharded model and for values other
+ * than 0 or 1.  cfd_set_state clears the published double, and the
+ * CFD_ETIMEOUT checkpoint covers it. */
+typedef struct {
+    int32_t residual_f64;      /* solves 2/4/5 publish the script's double; script updates decide from it */
+    int32_t residual_scaling;  /* residualScalingEnabled (index.html:338-348); implies residual_f64 */
+} cfd_script_options;
+int cfd_script_set_options(cfd_model *m, const cfd_script_options *o);
+int cfd_script_get_options(const cfd_model *m, cfd_script_options *o);
+/* last: the last solve's double residual; step_max: the maximum over the substeps of the last
+ * cfd_script_update (NULL skips either; 0.0 before the first such update).  Synchronises.
+ * CFD_ESTATE while residual_f64 is off, before a solve has published since the option was set or
+ * the state was replaced, and when the last solve was solver 0 or 1. */
+int cfd_get_p_residual_f64(cfd_model *m, double *last, double *step_max);
 
 /* The grid and parameters the model runs with (NULL skips either). */
 int cfd_get_config(const cfd_model *m, cfd_grid *grid, cfd_params *params);
