@@ -1,6 +1,7 @@
-// cfd_device.h — device helpers shared by the kernel translation units
-// (cfd_kernels.hip, cfd_jacobi_tb1.hip, cfd_jacobi_pipe.hip, ...).  Everything is
-// internal to each translation unit (anonymous namespace).
+// cfd_device.h — device helpers shared by every kernel translation unit (the
+// step kernels cfd_kernels.hip, the correctors cfd_correct.hip, the predictor
+// march, the Jacobi marches, the solvers and the script kernels).  Everything
+// is internal to each translation unit (anonymous namespace).
 #pragma once
 #include "cfd_internal.h"
 
@@ -11,9 +12,17 @@ namespace {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-
 constexpr int kBlock = 256;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// 16 bytes at a 4-byte aligned address (the u rows' pitch nx + 1): one
+// global_load/store_dwordx4 (unaligned access mode) instead of four dwords
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+
+// workgroups of a grid-stride launch over n4 items
+inline int copy_grid(size_t n4) {
+    long b = cdiv((long)n4, kBlock);
+    return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
+}
 
 __device__ __forceinline__ float dt_of(const Ctl *c, float dt_override) {
     return __builtin_isnan(dt_override) ? c->dt : dt_override;
@@ -160,6 +169,31 @@ template <int FAST>
 __device__ __forceinline__ double ddiv(double x, double c, double r) {
     if (FAST) return x * r;
     return x / c;
+}
+
+// rhs = div(u*, v*) / dt of 4 consecutive cells (model.rs:1406-1440): u0..u4
+// the cells' five u faces, vs / vn their south / north v faces.
+template <int SP>
+__device__ __forceinline__ float4 div4(const Geom &g, float u0, float u1, float u2, float u3,
+                                       float u4, const float4 &vs, const float4 &vn, float dt) {
+    const float rdx = g.r_dx, rdy = g.r_dy, dx = g.dx, dy = g.dy;
+    float4 r;
+    r.x = (sdiv<SP>(u1 - u0, dx, rdx) + sdiv<SP>(vn.x - vs.x, dy, rdy)) / dt;
+    r.y = (sdiv<SP>(u2 - u1, dx, rdx) + sdiv<SP>(vn.y - vs.y, dy, rdy)) / dt;
+    r.z = (sdiv<SP>(u3 - u2, dx, rdx) + sdiv<SP>(vn.z - vs.z, dy, rdy)) / dt;
+    r.w = (sdiv<SP>(u4 - u3, dx, rdx) + sdiv<SP>(vn.w - vs.w, dy, rdy)) / dt;
+    return r;
+}
+
+// Inlet face value of row j (model.rs:830-846): uniform or parabolic, >= 0.
+__device__ __forceinline__ float inlet_value(const Geom &g, float inlet, int j) {
+    if (g.profile == 0) return inlet;
+    const float y = ((float)j + 0.5f) * g.dy;
+    const float center = g.ly / 2.0f;
+    const float radius = g.ly / 2.0f;
+    const float q = (y - center) / radius;
+    const float pv = inlet * (1.0f - q * q);
+    return pv < 0.0f ? 0.0f : pv;
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));

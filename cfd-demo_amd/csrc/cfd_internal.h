@@ -1,6 +1,7 @@
 // cfd_internal.h — device-side data layout and kernel launch interface of the
-// MI355X pressure-projection path.  Shared by cfd_kernels.hip (device code)
-// and cfd_model.h / cfd_model_*.hip (host runtime behind include/cfd.h).
+// MI355X pressure-projection path.  Shared by the kernel units (cfd_device.h
+// and every csrc/*.hip that holds kernels) and by cfd_model.h /
+// cfd_model_*.hip (host runtime behind include/cfd.h).
 //
 // Layout in HBM (one slab per GPU; a single-GPU model is the 1-slab case):
 //   every field is row-major with x fastest and the reference's pitches
@@ -182,7 +183,13 @@ struct Fields {
     int32_t sums_track;
 };
 
-// ---- launchers (cfd_kernels.hip) ----
+// The float4 rows of the vector kernels: 16-byte aligned.  An invariant of
+// build_model (every field base is a hipMalloc base plus whole rows of nx
+// floats, nx % 8 == 0), which refuses a model that breaks it.
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// ---- step kernels (cfd_kernels.hip; the predictor march cfd_predict_march.hip,
+// the blocked Jacobi marches cfd_jacobi_*.hip) ----
 // pass < 0 means "not inside the corrector loop" (always runs).
 void launch_step_begin(const Geom &g, const Fields &f, int copy, hipStream_t s);
 void launch_copy_star(const Geom &g, const Fields &f, int pass, hipStream_t s);
@@ -191,8 +198,9 @@ void launch_copy_star_div(const Geom &g, const Fields &f, int pass, float dt_ove
                           hipStream_t s);
 void launch_u_predictor(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
 void launch_v_predictor(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
-// u and v predictors in one pass (same results as the two launches above).
-void launch_predict(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
+// u and v predictors in one pass (same results as the two launches above);
+// vec (cfd_options::pred_vec): the first-order scheme's four-column form.
+void launch_predict(const Geom &g, const Fields &f, float dt_override, bool vec, hipStream_t s);
 // both schemes' predictors + divergence in one row march (cfd_predict_march.hip),
 // when predict_march_ok(): replaces launch_predict + the step's first divergence
 bool predict_march_ok(const Geom &g, const Fields &f);
@@ -387,25 +395,9 @@ void launch_mg_tail(const MgLevel *dev_levels, int s_level, int coarsest, float 
                     int fast, const Ctl *ctl, int pass, hipStream_t s);
 void launch_mg_final_residual(const MgLevel &L, const float *p, uint32_t *slots, const Ctl *ctl,
                               int pass, hipStream_t s, unsigned long long *res64 = nullptr);
-void launch_corrector(const Geom &g, const Fields &f, int pass, float dt_override,
-                      hipStream_t s);
+// ---- velocity boundaries, step reduce and finalize (cfd_kernels.hip) ----
 void launch_boundary(const Geom &g, const Fields &f, hipStream_t s);
-// The corrector finish: the 16-row band march where the fields allow float4
-// access (nx % 4 == 0, 16-byte aligned arrays), else the scalar form.
-void launch_correct_finish(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
 void launch_step_reduce(const Geom &g, const Fields &f, hipStream_t s);
-// max |p'| bound of the fma form's guard after a step with corrector passes
-// (k_correct_finish4m publishes it itself); Fields::sums_track only
-void launch_publish_sums_m0(const Geom &g, const Fields &f, hipStream_t s);
-// The corrector of pass `pass` and, when pass+1 exists (has_next) and the
-// device's go flag says it runs, pass+1's head (u* <- u, v* <- v,
-// divergence) in one launch (k_correct_head4, single domain; every pass of the
-// loop uses it: the passes alternate the u* / v* arrays, and u / v are
-// written only when the loop ends); correct_head_ok: its alignment and
-// CFD_CORR_HEAD knob.
-bool correct_head_ok(const Geom &g, const Fields &f);
-void launch_correct_head(const Geom &g, const Fields &f, int pass, float dt_override, bool has_next,
-                         hipStream_t s);
 void launch_step_finalize(const Geom &g, const Fields &f, hipStream_t s);
 // Slabs with persistent runs (r5): copy this rank's abort word (persist[1],
 // a persistent solve timed out) into Ctl::red[6] before the step all-reduce
@@ -413,6 +405,27 @@ void launch_abort_to_red(const Fields &f, hipStream_t s);
 // ... and, after its all-reduce outside a step, back into this rank's abort
 // flag and host word (as the step finalize does)
 void launch_abort_from_red(const Fields &f, hipStream_t s);
+
+// ---- correctors (cfd_correct.hip) ----
+// apply_corrector as its own launch; vec (cfd_options::corr_vec): four cells
+// per thread, else the one-float-per-thread kernel.
+void launch_corrector(const Geom &g, const Fields &f, int pass, float dt_override, bool vec,
+                      hipStream_t s);
+// The corrector finish (corrector + boundaries + step maxima): the band march
+// of k_correct_finish4m.
+void launch_correct_finish(const Geom &g, const Fields &f, float dt_override, hipStream_t s);
+// max |p'| bound of the fma form's guard after a step with corrector passes
+// (k_correct_finish4m publishes it itself); Fields::sums_track only
+void launch_publish_sums_m0(const Geom &g, const Fields &f, hipStream_t s);
+// The corrector of pass `pass` and, when pass+1 exists (has_next) and the
+// device's go flag says it runs, pass+1's head (u* <- u, v* <- v,
+// divergence) in one launch (k_correct_head4, single domain; every pass of the
+// loop uses it: the passes alternate the u* / v* arrays, and u / v are
+// written only when the loop ends); correct_head_ok: its alignment (the
+// caller also asks cfd_options::corr_head).
+bool correct_head_ok(const Geom &g, const Fields &f);
+void launch_correct_head(const Geom &g, const Fields &f, int pass, float dt_override, bool has_next,
+                         hipStream_t s);
 
 // ---- tracer particles (cfd_tracers.hip; index.html:1472-1543) ----
 // The script's ordered list {x, y, initialY} as three f64 arrays in two buffers

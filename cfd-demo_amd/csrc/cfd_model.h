@@ -154,6 +154,9 @@ struct cfd_options {
     bool persist_gate = false;     // CFD_PERSIST_GATE (0): serialize persistent launches of different models on one device
     int resident = -1;             // CFD_RESIDENT (unset -1: up to kResidentAutoCells cells): 1 on any grid, 0 never
     bool copy_div = true;          // CFD_COPY_DIV (1): a pass head's copy and divergence as one launch; 0: two
+    bool pred_vec = true;          // CFD_PRED_VEC (1): the separate first-order predictors' four-column form; 0: one face per thread
+    bool corr_vec = true;          // CFD_CORR_VEC (1): the corrector's four-cell form; 0: one float per thread
+    bool corr_head = true;         // CFD_CORR_HEAD (1): a pass's corrector and the next pass's head as one launch; 0: separate
     bool graph = false;            // CFD_GRAPH (0): cfd_update_n replays a captured hipGraph of graph_steps steps
     bool ckpt = true;              // CFD_CKPT (1): self-recovery checkpoint; 0: a solve timeout invalidates the state
     int fastdiv = cfd::kEnvUnset;       // CFD_FASTDIV (unset: cheapest proven form): 0 IEEE division, 2 prefer the FMA-corrected form

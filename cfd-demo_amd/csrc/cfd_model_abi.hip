@@ -213,7 +213,7 @@ int cfd_run_phase(cfd_model *m, int phase, float dt_sub) {
         break;
     }
     case CFD_PHASE_DIVERGENCE: launch_divergence(m->g, m->f, -1, dt_sub, m->stream); break;
-    case CFD_PHASE_CORRECTOR: launch_corrector(m->g, m->f, -1, dt_sub, m->stream); break;
+    case CFD_PHASE_CORRECTOR: launch_corrector(m->g, m->f, -1, dt_sub, m->opt.corr_vec, m->stream); break;
     case CFD_PHASE_BOUNDARY: launch_boundary(m->g, m->f, m->stream); break;
     default: return fail(CFD_EINVAL, "unknown phase");
     }

@@ -23,6 +23,9 @@ cfd_options read_options() {
     o.persist_gate = env_flag("CFD_PERSIST_GATE", false);
     o.resident = env_int("CFD_RESIDENT", -1);
     o.copy_div = env_flag("CFD_COPY_DIV", true);
+    o.pred_vec = env_flag("CFD_PRED_VEC", true);
+    o.corr_vec = env_flag("CFD_CORR_VEC", true);
+    o.corr_head = env_flag("CFD_CORR_HEAD", true);
     o.graph = env_flag("CFD_GRAPH", false);
     o.ckpt = env_flag("CFD_CKPT", true);
     o.fastdiv = env_int("CFD_FASTDIV", kEnvUnset);
@@ -382,6 +385,12 @@ int build_model(cfd_model *m, const cfd_grid *grid, const cfd_params *p, int dev
     f.rhs = m->rhs + (size_t)hg * nx;   // hg ghost rows each side (sharded solves)
     f.pp[0] = m->pp_all[0] + (size_t)hg * nx;
     f.pp[1] = m->pp_all[1] + (size_t)hg * nx;
+    // the vector kernels move these rows as float4 (aligned16, cfd_internal.h)
+    const std::pair<const float *, const char *> rows16[] = {
+        {f.v, "v"}, {f.v_star, "v_star"}, {f.p, "p"}, {f.rhs, "rhs"}, {f.pp[0], "pp[0]"}, {f.pp[1], "pp[1]"}};
+    for (const auto &r : rows16)
+        if (!aligned16(r.first))
+            return fail(CFD_EINVAL, std::string("field ") + r.second + " is not 16-byte aligned");
     f.mask_u = m->mask_u;
     f.mask_v = m->mask_v;
     f.obs = m->obs;

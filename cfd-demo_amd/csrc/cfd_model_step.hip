@@ -73,7 +73,7 @@ int cfd_model::enqueue_piso(float dt_override, bool finish) {
     } else if (march)
         launch_predict_march(g, f, dt_override, stream, finish && step_begin_folded);
     else
-        launch_predict(g, f, dt_override, stream);
+        launch_predict(g, f, dt_override, opt.pred_vec, stream);
     auto first_divergence = [&](int pass) {
         if (!march) launch_divergence(g, f, pass, dt_override, stream);
         phase_mark(0, true);
@@ -102,12 +102,12 @@ int cfd_model::enqueue_piso(float dt_override, bool finish) {
         // (k_correct_head4; every pass, the last included, runs it: the
         // passes alternate the u* / v* arrays)
         const int passes = params.corrector_passes;
-        const bool fuse = !sharded() && passes >= 1 && correct_head_ok(g, f);
+        const bool fuse = !sharded() && passes >= 1 && opt.corr_head && correct_head_ok(g, f);
         auto corrector = [&](int pass) {
             if (fuse)
                 launch_correct_head(g, f, pass, dt_override, pass < passes, stream);
             else
-                launch_corrector(g, f, pass, dt_override, stream);
+                launch_corrector(g, f, pass, dt_override, opt.corr_vec, stream);
         };
         corrector(0);
         const bool spec_slabs = sharded() && g.tol_enabled && spec_slab_ok();
@@ -125,12 +125,12 @@ int cfd_model::enqueue_piso(float dt_override, bool finish) {
         float res = 0.f;
         int rc = enqueue_solve_host_driven(&res);
         if (rc) return rc;
-        launch_corrector(g, f, -1, dt_override, stream);
+        launch_corrector(g, f, -1, dt_override, opt.corr_vec, stream);
         for (int pass = 1; pass <= params.corrector_passes; ++pass) {
             pass_head(-1, dt_override);
             rc = enqueue_solve_host_driven(&res);
             if (rc) return rc;
-            launch_corrector(g, f, -1, dt_override, stream);
+            launch_corrector(g, f, -1, dt_override, opt.corr_vec, stream);
             if (res < params.p_tol) break;
         }
     }

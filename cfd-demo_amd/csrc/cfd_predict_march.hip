@@ -25,8 +25,8 @@
 // face nx, the one face of its chunk that exists.
 //
 // The face arithmetic is u_pred_val / v_pred_val (cfd_predict.h) over a
-// register accessor and the divergence is k_divergence's expression, so the
-// results are the unfused kernels', bit for bit.  Faces the reference does not
+// register accessor and the divergence is k_divergence's div4 (cfd_device.h),
+// so the results are the unfused kernels', bit for bit.  Faces the reference does not
 // predict (face 0, v column 0, rows outside glo..u_hi / v_hi) are read from
 // memory, as k_divergence reads them.
 #include "cfd_device.h"
@@ -47,8 +47,6 @@ namespace {
 #ifndef CFD_PM_PD
 #define CFD_PM_PD 1   // prefetch distance (steps) of the u / v rows (1: 88.6 vs 90.3 us SO, r2 pm)
 #endif
-
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
 // Stencil accessor over the step's windows: u / v row k - 2 + r in x[r],
 // columns i0-2..i0+5 at index 2 + column - i0; C = window row of the face.
@@ -197,12 +195,9 @@ struct PredMarch {
                             f.u_star[ku + 3] = us[3];
                         }
                     }
-                    const float rdx = g->r_dx, rdy = g->r_dy, dx = g->dx, dy = g->dy;
-                    float4 rh;
-                    rh.x = (sdiv<SP>(us[1] - us[0], dx, rdx) + sdiv<SP>(vn[0] - vs[0], dy, rdy)) / dt;
-                    rh.y = (sdiv<SP>(us[2] - us[1], dx, rdx) + sdiv<SP>(vn[1] - vs[1], dy, rdy)) / dt;
-                    rh.z = (sdiv<SP>(us[3] - us[2], dx, rdx) + sdiv<SP>(vn[2] - vs[2], dy, rdy)) / dt;
-                    rh.w = (sdiv<SP>(east - us[3], dx, rdx) + sdiv<SP>(vn[3] - vs[3], dy, rdy)) / dt;
+                    const float4 rh = div4<SP>(*g, us[0], us[1], us[2], us[3], east,
+                                               make_float4(vs[0], vs[1], vs[2], vs[3]),
+                                               make_float4(vn[0], vn[1], vn[2], vn[3]), dt);
                     *reinterpret_cast<float4 *>(f.rhs + (long)k * nx + i0) = rh;
                     if (f.sums_track)
                         rmax = max(max(rmax, max(abs_bits(rh.x), abs_bits(rh.y))),
@@ -316,9 +311,8 @@ __global__ __launch_bounds__(kBlock, CFD_PM_WPE) void k_predict_march(Geom g, Fi
 }  // namespace
 
 bool predict_march_ok(const Geom &g, const Fields &f) {
-    auto a16 = [](const void *p) { return ((uintptr_t)p & 15u) == 0; };
-    return g.pred_div == 2 && g.nx % 4 == 0 && g.nx >= 8 && g.nyl >= 4 && a16(f.v) && a16(f.v_star) &&
-           a16(f.rhs) && (uint64_t)f.u_alloc * 4u < (1ull << 31) &&
+    return g.pred_div == 2 && g.nx % 4 == 0 && g.nx >= 8 && g.nyl >= 4 && aligned16(f.v) &&
+           aligned16(f.v_star) && aligned16(f.rhs) && (uint64_t)f.u_alloc * 4u < (1ull << 31) &&
            (uint64_t)f.v_alloc * 4u < (1ull << 31);
 }
 

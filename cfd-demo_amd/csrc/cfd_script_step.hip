@@ -41,8 +41,6 @@
 namespace cfd {
 namespace {
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-
 // register windows of a step: u row k-2+r in u[r], v row k-1+r in v[r],
 // columns i0-2..i0+5 at index 2 + column - i0; CU / CV: window rows of the
 // face's own u / v row

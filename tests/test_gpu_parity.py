@@ -134,7 +134,7 @@ def test_live_oracle_channel_nonsquare(scheme):
 @pytest.mark.parametrize("scheme,profile,tol", [(0, 0, 1), (1, 1, 0), (0, 1, 0), (1, 0, 1)])
 def test_fused_finish_channel(scheme, profile, tol):
     """corrector_passes 0 runs corrector + boundaries + step residuals as one fused
-    kernel (k_correct_finish): channel with the cylinder (outflow copy, obstacle
+    kernel (k_correct_finish4m): channel with the cylinder (outflow copy, obstacle
     faces, uniform/parabolic inlet), residuals compared every step."""
     c = _cfd()
     g = dict(nx=192, ny=96, lx=30.0, ly=10.0, cylinder=(7.5, 5.0, 1.5))
@@ -193,6 +193,48 @@ def test_predict_div_fused_matches_unfused(monkeypatch, case):
     for mode in modes[1:]:
         for f in ("u", "v", "p", "u_star", "v_star", "p_prime", "rhs"):
             assert_bitwise(f"{f} (CFD_PRED_DIV={mode})", out[mode][f], out["0"][f])
+
+
+@pytest.mark.parametrize("g", [
+    dict(nx=16, ny=5, lx=3.0, ly=1.0, cylinder=None),
+    dict(nx=264, ny=7, lx=30.0, ly=1.0, cylinder=(7.5, 0.5, 0.3)),
+    dict(nx=1032, ny=6, lx=30.0, ly=1.0, cylinder=None),
+], ids=["16x5", "264x7_cylinder", "1032x6"])
+def test_predict_vec_matches_scalar(monkeypatch, g):
+    """The separate first-order predictors (CFD_PRED_DIV=0): four columns and
+    two rows per thread (k_predict4r<.,2>, CFD_PRED_VEC=1) against one face per
+    thread (k_predict<0,.>, CFD_PRED_VEC=0), two updates from a random u, v of
+    both signs, every field bitwise between the two and against the oracle.
+    16 x 5: the smallest nx (one lane holds i0 == 0, three lanes on face nx),
+    odd rows and the clamped last row pair; 264 x 7: 66 lanes, obstacle masks,
+    outflow; 1032 x 6: nx/4 = 258 lanes, the seam between two workgroups."""
+    c = _cfd()
+    kw = dict(scheme=0, jacobi_iters=10, corrector_passes=0, tol_enabled=False)
+    fields = ("u_star", "v_star", "rhs", "u", "v", "p")
+    rng = np.random.default_rng(g["nx"])
+    o = _oracle(g, **kw)
+    u0 = rng.uniform(-0.5, 0.5, o.field("u").shape).astype(np.float32)
+    v0 = rng.uniform(-0.5, 0.5, o.field("v").shape).astype(np.float32)
+    o.field("u")[:] = u0
+    o.field("v")[:] = v0
+    for _ in range(2):
+        o.update()
+    monkeypatch.setenv("CFD_PRED_DIV", "0")
+    got = {}
+    for vec in ("0", "1"):
+        monkeypatch.setenv("CFD_PRED_VEC", vec)
+        m = c.Model(_grid(g), _params(kw))
+        try:
+            m.set_state(u=u0, v=v0)
+            for _ in range(2):
+                m.update()
+            got[vec] = m.get_state()
+        finally:
+            m.close()
+    tag = f"{g['nx']}x{g['ny']}"
+    for f in fields:
+        assert_bitwise(f"{tag} predictors vec vs scalar:{f}", got["1"][f], got["0"][f])
+        assert_bitwise(f"{tag} predictors vec vs oracle:{f}", got["1"][f], o.field(f))
 
 
 def test_jacobi_tolerance_and_fixed_paths():
