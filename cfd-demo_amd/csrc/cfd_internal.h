@@ -20,9 +20,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/cfd.h"
 
 namespace cfd {
+
+// Calls f with the division mode (Geom::fastdiv: 1, 2, anything else 0) as a
+// std::integral_constant, so a generic lambda can name the kernel
+// instantiation (k<T, F()>); returns what f returns.
+template <class Fn>
+auto with_fastdiv(int fastdiv, Fn &&f) {
+    if (fastdiv == 1) return f(std::integral_constant<int, 1>{});
+    if (fastdiv == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
+}
 
 constexpr int kGhostUV = 2;
 // thresholds of the fma form's bounds (Ctl::sums_m0 / sums_rm): R max|p'| <=
@@ -235,7 +247,7 @@ bool launch_jacobi_persist(const Geom &g, const Fields &f, int pass, int par0, i
 // The tile geometry of the T = 8 kind-5 launch over rows [out_lo, out_hi)
 // (persist: the persistent form's): dynamic LDS pad, workgroups per CU the
 // round is sized for, wave columns, wave segments per column
-// (cfd_jacobi_lds8.hip).
+// (cfd_jacobi_lds8.hip, from the launches' own lds_tiles, cfd_jacobi_lds.hip).
 void lds_geometry8(const Geom &g, int out_lo, int out_hi, bool persist, int *pad, int *occ, int *nwc,
                    int *nseg);
 // The block kernels behind it: k_jacobi_tb (kind 1, T <= 4, cfd_jacobi_tb1.hip)
@@ -246,8 +258,10 @@ void launch_tb1(const Geom &g, const Fields &f, int T, int pass, int it, int par
                 int out_hi, uint32_t *res_slots, hipStream_t s);
 void launch_pipe(const Geom &g, const Fields &f, int T, int pass, int it, int par, int out_lo,
                  int out_hi, uint32_t *res_slots, hipStream_t s);
-// kind 5: the same march with its rhs window in LDS (cfd_jacobi_lds.hip, T <= 8);
-// mode 2 / 3: the speculative launch / its re-run (launch_jacobi_spec)
+// kind 5: the same march with its rhs window in LDS: its persistent form
+// (cfd_jacobi_lds_persist.hip, T = 8) and its per-launch form
+// (cfd_jacobi_lds.hip, T <= 8); mode 2 / 3: the speculative launch / its re-run
+// (launch_jacobi_spec)
 bool launch_lds_persist8(const Geom &g, const Fields &f, int pass, int par0, int nblk, int out_lo,
                          int out_hi, uint32_t epoch, uint32_t *rs, hipStream_t s);
 // lag (r5, speculative solves on one domain): mode 2 -- the previous launch's

@@ -1,10 +1,12 @@
 // cfd_jacobi_lds.h — kind 5: the temporally blocked Jacobi march
 // (model.rs:748-815, T sweeps per launch) with its rhs window in LDS.
-// Included by three translation units that instantiate it for disjoint sets
-// of T (cfd_jacobi_lds.hip: T <= 4 and the dispatch, cfd_jacobi_lds567.hip,
-// cfd_jacobi_lds8.hip), so the kind's compile runs in parallel.
+// Included by the translation units that instantiate it for disjoint sets
+// of T (cfd_jacobi_lds.hip: T <= 4, the dispatch and the host-side tile
+// geometry; cfd_jacobi_lds567.hip; cfd_jacobi_lds8.hip), so the kind's compile
+// runs in parallel, and by cfd_jacobi_lds_persist.hip, whose persistent kernel
+// runs the same block (lds_block) once per task.
 //
-// Same schedule as the prefetch-pipelined march (cfd_jacobi_pipe.h): a wave
+// Same schedule as the prefetch-pipelined march (cfd_jacobi_pipe.hip): a wave
 // owns 64 lanes x 2 columns of a row segment and marches along it; stage s
 // (1..T) of slot v computes row k-s (k = k_first + v) from stage s-1's rows
 // k-s-1..k-s+1, so every stage is one sweep of the reference, bit for bit.
@@ -23,8 +25,8 @@
 //
 // The horizontal neighbour sums are written as two scalar adds whose second
 // operand is a DPP lane shift (wave_shr:1 / wave_shl:1): the backend folds
-// each shift into its add (v_add_f32_dpp), one VALU instruction per sum.  This
-// translation unit is built with -fno-slp-vectorize so the two adds are not
+// each shift into its add (v_add_f32_dpp), one VALU instruction per sum.  The
+// kind-5 units are built with -fno-slp-vectorize so the two adds are not
 // packed back into a v_pk_add_f32 (VOP3P cannot take DPP); the rest of the
 // update is explicit packed f32 arithmetic on column pairs.
 #pragma once
@@ -33,67 +35,103 @@
 
 #include "cfd_device.h"
 
-namespace cfd {
-namespace {
-
-constexpr int kLdsWaves = 4;   // waves per workgroup (256 threads)
-#ifndef CFD_LDS_SB
-#define CFD_LDS_SB 0   // scheduling barriers: 1 between slots, 2 also between stages
-#endif                 // (bound live ranges; measured no faster, r2 ab_lds_R*.log)
+// Build-time constants of the march, each with the A/B that set it.  A variant
+// build of one unit (tools/build_variants.sh) overrides them with -D.
 #ifndef CFD_LDS_PD
-#define CFD_LDS_PD 3   // prefetch distance (slots) of the p' and rhs rows
+#define CFD_LDS_PD 3        // prefetch distance (slots) of the p' and rhs rows; 4: 5.07 vs 4.95 us/sweep (r6 abvar_kvar.log)
 #endif
-// CFD_LDS_DIAG (timing diagnostics only, WRONG results), bits: 1 = no global
-// loads (rows are a lane constant), 2 = no LDS ring (stage s reads the
-// register prefetch of another row), 4 = no p' stores.  At 4096^2 (r6,
-// profiles/r6/prof_r6q/abvar_diag.log): 5.03 us per sweep; without stores
-// 4.46, without loads 4.15, without both 4.06.  gfx950 counts a wave's loads
-// and stores in ONE vmcnt, in issue order, so each wait for a prefetched row
-// also waits for the p' stores issued before it: the stores cost through that
-// coupling.  A fifth "store wave" per workgroup draining LDS rings of the
-// output rows measured slower (5.79; 5.22 even with its stores and ring waits
-// compiled out -- the 96-VGPR cap that 5 waves per SIMD need, and the fifth
-// wave shares wave 0's SIMD: profiles/r6/prof_r6t, prof_r6s/wave_place.log).
-#ifndef CFD_LDS_DIAG
-#define CFD_LDS_DIAG 0
+#ifndef CFD_LDS_SPLIT
+#define CFD_LDS_SPLIT 1     // stage groups per slot (LdsMarch::G); 2: 5.25 vs 4.95 us/sweep (r6 prof_r6c/abvar_kvar.log)
 #endif
-#ifndef CFD_LDS_WPE
-#define CFD_LDS_WPE 0  // > 0: minimum waves per SIMD for the register allocation
-#endif
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-// CFD_LDS_STAMP (diagnostic builds only): every wave of a RES=false launch
-// records its start and end (s_memrealtime, 100 MHz), its shader-clock span
-// (s_memtime) and its HW_ID / XCC_ID in g_lds_stamp (vector stores), read back
-// by cfd_diag_lds_stamps.  Off in the product build.
 #ifndef CFD_LDS_PRIO
-#define CFD_LDS_PRIO 1  // progress-ordered issue priority (LdsMarch::set_prio)
+#define CFD_LDS_PRIO 1      // progress-ordered issue priority (LdsMarch::set_prio); 0: waves end 21..39 us apart (r2 timeline)
 #endif
-#ifndef CFD_LDS_COMPACT
-#define CFD_LDS_COMPACT 0  // 1: warm-up and tail share one run-time-guarded slot group
+#ifndef CFD_LDS_ST_AUX
+#define CFD_LDS_ST_AUX 16   // p' stores write-through (sc1): 5.07 vs 5.13 us/sweep plain, nt 5.78 (r3 ab_staux.log)
+#endif
+#ifndef CFD_LDS_SPEC_WPE
+#define CFD_LDS_SPEC_WPE 5  // SPEC launch's waves per SIMD (4 unpinned, at 99 VGPRs): T = 8 69.7 -> 58.5 us, a few spills
+#endif
+#ifndef CFD_PERSIST_WPE
+#define CFD_PERSIST_WPE 3   // k_jacobi_persist: the padded launch's 3 waves per SIMD, at most 168 VGPRs
 #endif
 #ifndef CFD_LDS_STAMP
-#define CFD_LDS_STAMP 0
+#define CFD_LDS_STAMP 0     // diagnostic builds: the wave timeline below (tools/lds_stamps.py)
 #endif
+
+namespace cfd {
+
+constexpr int kLdsWaves = 4;   // waves per workgroup (256 threads)
+
 #if CFD_LDS_STAMP
+// The wave timeline of a stamp build (one unit compiled with -DCFD_LDS_STAMP=1,
+// by default cfd_jacobi_lds8): every wave of a RES=false launch records its
+// start and end (s_memrealtime, 100 MHz), its shader-clock span (s_memtime)
+// and its HW_ID / XCC_ID in g_lds_stamp (vector stores); cfd_diag_lds_stamps
+// reads that unit's array back.  Off in the product build.
+namespace {
 constexpr int kStampWaves = 1 << 15;
 __device__ unsigned long long g_lds_stamp[kStampWaves * 4];
+template <bool RES>
+struct StampOnExit {
+    unsigned long long rt0, t0;
+    unsigned long long bid;   // the XCD-renumbered block (tile: bid % nwc, row group bid / nwc)
+    __device__ explicit StampOnExit(int b)
+        : rt0(__builtin_amdgcn_s_memrealtime()), t0(__builtin_amdgcn_s_memtime()),
+          bid((unsigned long long)b) {}
+    __device__ ~StampOnExit() {
+        if (RES) return;
+        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+        // hwreg(id, 0, 32): HW_ID = 4, XCC_ID = 20
+        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));
+        const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+        const int idx = (int)blockIdx.x * kLdsWaves + ((int)threadIdx.x >> 6);
+        if ((threadIdx.x & 63) == 0 && idx < kStampWaves) {
+            g_lds_stamp[idx * 4 + 0] = rt0;
+            g_lds_stamp[idx * 4 + 1] = rt1;
+            g_lds_stamp[idx * 4 + 2] = (bid << 40) | ((t1 - t0) & 0xFFFFFFFFFFull);
+            g_lds_stamp[idx * 4 + 3] = ((unsigned long long)xcc << 32) | hw;
+        }
+    }
+};
+}  // namespace
+extern "C" int cfd_diag_lds_stamps(unsigned long long *host, int nwaves) {
+    if (nwaves > kStampWaves) nwaves = kStampWaves;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_lds_stamp), (size_t)nwaves * 32, 0,
+                               hipMemcpyDeviceToHost) == hipSuccess ? nwaves : -1;
+}
 #endif
 
-#ifndef CFD_LDS_ST_AUX
-#define CFD_LDS_ST_AUX 16  // p' stores write-through (sc1): 5.07 vs 5.13 us/sweep plain, nt 5.78 (r3 ab_staux.log)
-#endif
+// lanes of a wave whose columns are stored: 64 minus (T + 1) / 2 halo lanes
+// per side (2 columns per lane)
+constexpr int lds_outl(int T) { return 64 - 2 * ((T + 1) / 2); }
 
-#ifndef CFD_LDS_LD_AUX
-#define CFD_LDS_LD_AUX 0  // cache-policy bits of the p' loads (16 = sc1: bypass L1)
-#endif
+// The tile geometry of a kind-5 launch: dynamic LDS pad (bytes), wave columns,
+// wave segments per column, and the row weights of a column's first / last
+// segment (lds_block splits the rows in proportion; 16 = an interior one).
+struct LdsTiles {
+    int pad, nwc, nseg, wlo, whi;
+};
+// Fills it (cfd_jacobi_lds.hip) for T sweeps over rows [out_lo, out_hi) in
+// `mode` (LdsMarch MODE).  bpc: workgroups of the caller's kernel one CU holds
+// with lds_pad_bytes(g, mode) of dynamic LDS (its occupancy query).
+// one_round: the persistent form's single round of resident workgroups.
+LdsTiles lds_tiles(const Geom &g, int T, int out_lo, int out_hi, int mode, int bpc, bool one_round);
+int lds_pad_bytes(const Geom &g, int mode);
+bool lds_sums_grid(const Geom &g);
 
-#ifndef CFD_LDS_HOIST
-#define CFD_LDS_HOIST 0  // 1: read a slot's T rhs rows from the LDS ring at its start (r2: 5.09 vs 5.00 us/sweep, off)
-#endif
+// per-translation-unit entry points (cfd_jacobi_lds*.hip)
+void launch_lds_t567(const Geom &g, const Fields &f, int T, int pass, int par, int it, int out_lo,
+                     int out_hi, uint32_t *rs, int mode, hipStream_t s, int lag);
+void launch_lds_t8(const Geom &g, const Fields &f, int pass, int par, int it, int out_lo, int out_hi,
+                   uint32_t *rs, int mode, hipStream_t s, int lag);
+// workgroups of k_jacobi_persist<8, g.fastdiv> per CU (cfd_jacobi_lds_persist.hip)
+int persist_blocks_per_cu8(const Geom &g, int pad);
 
-#ifndef CFD_LDS_SPLIT
-#define CFD_LDS_SPLIT 1  // independent stage groups per slot (see LdsMarch)
-#endif
+namespace {
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 constexpr int lds_gcd(int a, int b) { return b == 0 ? a : lds_gcd(b, a % b); }
 // Slots of lag accumulated before stage s when the T stages form G groups,
 // each group one slot behind the one before it.
@@ -147,13 +185,10 @@ struct LdsMarch {
     // needs: max |p'| of the rows the wave loads (imax) and of the rhs rows it
     // uses (rmax); every persistent block tracks max |p'| of the rows it
     // stores (omax), which are its neighbours' inputs in the next block
-#ifndef CFD_PROBE_NOTRACK
-#define CFD_PROBE_NOTRACK 0   // (diagnostic builds: no guard tracking)
-#endif
-    static constexpr bool TRACK_IN = PERSIST && !SUMS && !CFD_PROBE_NOTRACK;
-    static constexpr bool TRACK_OUT = PERSIST && !CFD_PROBE_NOTRACK;
+    static constexpr bool TRACK_IN = PERSIST && !SUMS;
+    static constexpr bool TRACK_OUT = PERSIST;
     static_assert(!SUMS || FAST == 1, "SUMS: reciprocal multiply");
-    static constexpr int PLD_AUX = PERSIST ? 16 : CFD_LDS_LD_AUX;
+    static constexpr int PLD_AUX = PERSIST ? 16 : 0;
     static constexpr int PST_AUX = PERSIST ? 16 : CFD_LDS_ST_AUX;
     // Stage s of slot v computes row k - s - off(s).  With G = 1 (off = 0)
     // this is the plain pipeline: stage s reads stage s-1's row of the SAME
@@ -164,6 +199,10 @@ struct LdsMarch {
     // that hides the packed-f32 result latency), for one more window row per
     // stage (NW = 4) and off(T) more warm-up and ring rows.  The set of
     // (stage, row) updates is the same, and so is every value.
+    // (G = 2 lost its A/B, but off(s) stays in the source: with it folded to
+    // 0 by hand the optimiser sees the stage loop differently before it
+    // unrolls, and 31 k_jacobi_lds instantiations come out with other
+    // instruction streams -- profiles/r10/isa_compare.md.)
     static constexpr int G = CFD_LDS_SPLIT;
     static constexpr int NW = lds_nw(G);            // register window rows per stage
     static constexpr int PD = CFD_LDS_PD;           // prefetch distance (slots) of p' and rhs
@@ -172,7 +211,7 @@ struct LdsMarch {
     static constexpr int U = D;                     // slot unroll: every ring index compile-time
     static constexpr int WARM = 2 * T + OFFT;       // stage s starts at slot 2s + off(s)
     static constexpr int H = (T + 1) / 2;           // halo lanes per side (2 columns per lane)
-    static constexpr int OUTL = 64 - 2 * H;         // lanes whose columns are stored
+    static constexpr int OUTL = lds_outl(T);        // lanes whose columns are stored
     static constexpr int off(int s) { return lds_off(s, T, G); }
     static constexpr int start(int s) { return 2 * s + off(s); }
     static_assert(D % PD == 0 && D % NW == 0 && D >= T + OFFT + 1, "ring geometry");
@@ -212,7 +251,6 @@ struct LdsMarch {
     // (their values only reach halo rows that the boundary patch overwrites).
     template <int AUX = 0>
     __device__ __forceinline__ f2 ld(__amdgpu_buffer_rsrc_t rs, int vrow) const {
-        if (CFD_LDS_DIAG & 1) return (f2){__int_as_float(vo_ld + vrow), 1.0f};
         vrow = vrow < k_first + S ? vrow : k_first + S - 1;
         int row = act(vrow);
         row = row < lo_clamp ? lo_clamp : (row > hi_clamp ? hi_clamp : row);
@@ -220,10 +258,6 @@ struct LdsMarch {
         return (f2){__uint_as_float(v.x), __uint_as_float(v.y)};
     }
     __device__ __forceinline__ void st(const f2 &x, int row) const {
-        if (CFD_LDS_DIAG & 4) {   // keep the value live without storing it
-            asm volatile("" ::"v"(x.x), "v"(x.y));
-            return;
-        }
         const u32x2 v = {__float_as_uint(x.x), __float_as_uint(x.y)};
         __builtin_amdgcn_raw_buffer_store_b64(v, rs_d, vo_st, (row - wbase) * row_bytes, PST_AUX);
     }
@@ -274,35 +308,21 @@ struct LdsMarch {
     }
 
     // Slot v (k = k_first + v), V_ == v (mod U).  GUARD 0: warm-up (V_ == v,
-    // stage s runs from slot start(s) on); GUARD 2: the final partial group;
-    // GUARD 3: both, decided at run time (CFD_LDS_COMPACT).
+    // stage s runs from slot start(s) on); 1: a full group; 2: the final
+    // partial group.
     template <int V_, int GUARD, int E>
     __device__ __forceinline__ void slot(int v) {
-        if ((GUARD == 2 || GUARD == 3) && v >= S) return;
-        if (CFD_LDS_SB >= 1) __builtin_amdgcn_sched_barrier(0);
+        if (GUARD == 2 && v >= S) return;
         const int k = k_first + v;
         W[0][V_ % NW] = PQ[V_ % PD];                                 // input row k
         PQ[V_ % PD] = ld<PLD_AUX>(rs_p, k + PD);
-        if (!(CFD_LDS_DIAG & 2))
-            ring[(V_ % D) * 64 + lane] = RQ[V_ % PD];                 // rhs row k
+        ring[(V_ % D) * 64 + lane] = RQ[V_ % PD];                    // rhs row k
         RQ[V_ % PD] = ld(rs_r, k + PD);
-        // the slot's T ring reads issued together (the ring rows of earlier
-        // slots; this slot's write went to another entry): one LDS latency
-        // per slot instead of one per stage
-        f2 rhv[T];
-        if (CFD_LDS_HOIST && !(CFD_LDS_DIAG & 2)) {
-#pragma unroll
-            for (int s = 1; s <= T; ++s) rhv[s - 1] = ring[((V_ - s - off(s) + 8 * D) % D) * 64 + lane];
-        }
 #pragma unroll
         for (int s = 1; s <= T; ++s) {
             if (GUARD == 0 && V_ < start(s)) continue;               // compile-time
-            if (GUARD == 3 && v < start(s)) continue;                // wave-uniform
-            if (CFD_LDS_SB >= 2 && s > 1) __builtin_amdgcn_sched_barrier(0);
             const int r = k - s - off(s);
-            const f2 rh = (CFD_LDS_DIAG & 2) ? RQ[(V_ + s) % PD]
-                                             : (CFD_LDS_HOIST ? rhv[s - 1]
-                                                              : ring[((V_ - s - off(s) + 8 * D) % D) * 64 + lane]);
+            const f2 rh = ring[((V_ - s - off(s) + 8 * D) % D) * 64 + lane];
             // stage s-1 finished row r+1 in slot v - dl (dl = 0 inside a
             // group, 1 at a group's first stage), row r one slot earlier, ...
             constexpr int kW = 4 * NW;
@@ -374,11 +394,7 @@ struct LdsMarch {
                 st(n, ra);
                 if ((E & kRow) && r == g_first) st(n, g_zero);
                 if ((E & kRow) && r == g_last) st(n, g_top);
-#ifndef CFD_PROBE_NOOMAX
-#define CFD_PROBE_NOOMAX 0
-#endif
-                if constexpr (TRACK_OUT && !CFD_PROBE_NOOMAX)
-                    omax = fmaxf(fmaxf(omax, fabsf(n.x)), fabsf(n.y));
+                if constexpr (TRACK_OUT) omax = fmaxf(fmaxf(omax, fabsf(n.x)), fabsf(n.y));
             }
         }
     }
@@ -391,12 +407,12 @@ struct LdsMarch {
         }
     }
 
-    // U slots from `base`; OFF == base (mod U)
-    template <int J, int GUARD, int E, int OFF = WARM>
+    // U slots from `base`; WARM == base (mod U)
+    template <int J, int GUARD, int E>
     __device__ __forceinline__ void group(int base) {
         if constexpr (J < U) {
-            slot<OFF + J, GUARD, E>(base + J);
-            group<J + 1, GUARD, E, OFF>(base);
+            slot<WARM + J, GUARD, E>(base + J);
+            group<J + 1, GUARD, E>(base);
         }
     }
 
@@ -426,22 +442,6 @@ struct LdsMarch {
     // per-group switch between paths costs ~15 VGPRs of phi copies.
     template <int E>
     __device__ __forceinline__ void run() {
-        if (CFD_LDS_COMPACT) {
-            // warm-up and tail through one run-time-guarded group: half the
-            // code of the unrolled warm-up + guarded tail (2U >= WARM)
-            static_assert(2 * U >= WARM, "warm-up fits two groups");
-            set_prio(0);
-            group<0, 3, E, 0>(0);
-            group<0, 3, E, 0>(U);
-            int base = 2 * U;
-            for (; base + U <= S; base += U) {
-                set_prio(base - WARM);
-                group<0, 1, E, 0>(base);
-            }
-            set_prio(base - WARM);
-            if (base < S) group<0, 3, E, 0>(base);
-            return;
-        }
         set_prio(0);
         warmup<0, E>();
         int base = WARM;
@@ -602,12 +602,7 @@ __device__ __forceinline__ void lds_block(const Geom &g, float *__restrict__ pa,
 // Minimum waves per SIMD the register allocation must allow (the SPEC
 // launch holds T residual maxima on top of the plain march: 99 VGPRs, 4
 // waves; pinned to 5 it spills).
-#ifndef CFD_LDS_SPEC_WPE
-#define CFD_LDS_SPEC_WPE 5
-#endif
-constexpr int lds_min_waves(int mode) {
-    return mode == 2 ? CFD_LDS_SPEC_WPE : (CFD_LDS_WPE > 0 ? CFD_LDS_WPE : 1);
-}
+constexpr int lds_min_waves(int mode) { return mode == 2 ? CFD_LDS_SPEC_WPE : 1; }
 // The lagged early-exit check (r5, single-domain speculative solves; replaces
 // the one-workgroup k_spec_check launch after every speculative launch): each
 // workgroup of the NEXT launch folds the T residual slot sets of launch lpar
@@ -645,30 +640,9 @@ __global__ __launch_bounds__(kLdsWaves * 64, lds_min_waves(MODE)) void k_jacobi_
     Ctl *ctl, uint32_t *res_slots, int pass, int par, int out_lo, int out_hi, int nwc, int nseg,
     int wlo, int whi, int it, int lag, float sums_c) {
     using M = LdsMarch<T, FAST, MODE>;
-    [[maybe_unused]] constexpr bool RES = M::RES;   // the stamp guard's
     __shared__ f2 lds[kLdsWaves * M::D * 64];
 #if CFD_LDS_STAMP
-    const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
-    struct StampOnExit {
-        unsigned long long rt0, t0;
-        unsigned long long bid;   // the XCD-renumbered block (tile: bid % nwc, row group bid / nwc)
-        __device__ ~StampOnExit() {
-            if (RES) return;
-            const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-            // hwreg(id, 0, 32): HW_ID = 4, XCC_ID = 20
-            const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));
-            const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
-            const int idx = (int)blockIdx.x * kLdsWaves + ((int)threadIdx.x >> 6);
-            if ((threadIdx.x & 63) == 0 && idx < kStampWaves) {
-                g_lds_stamp[idx * 4 + 0] = rt0;
-                g_lds_stamp[idx * 4 + 1] = rt1;
-                g_lds_stamp[idx * 4 + 2] = (bid << 40) | ((t1 - t0) & 0xFFFFFFFFFFull);
-                g_lds_stamp[idx * 4 + 3] = ((unsigned long long)xcc << 32) | hw;
-            }
-        }
-    } stamp_guard{st_rt0, st_t0, (unsigned long long)xcd_block(g)};
+    StampOnExit<M::RES> stamp_guard(xcd_block(g));
 #endif
     if (pass_off(ctl, pass)) return;
     int nst = 0;
@@ -727,357 +701,8 @@ __global__ __launch_bounds__(kLdsWaves * 64, lds_min_waves(MODE)) void k_jacobi_
                              whi, lds, nst, xcd_block(g));
 }
 
-// Persistent fixed-count solve: ONE launch runs nblk blocks of T sweeps
-// (par0.. launches of the per-launch form) over ntiles tiles (tile = the four
-// wave segments of one workgroup of the per-launch form).  Task (t, b), block
-// b of tile t, reads the rows that t and its 3 x 3 neighbours (adjacent wave
-// columns hold the halo lanes' columns, adjacent row groups the T-row input
-// bands) wrote in block b-1, and overwrites the buffer they read in block
-// b-1, so it starts once all nine have finished block b-1 — no launch
-// boundary, no grid-wide drain, and a slow tile holds back only its
-// neighbours.
-//
-// Ownership with stealing.  Workgroup w owns tile w (XCD-renumbered, as the
-// per-launch form maps it) and runs its blocks in order, so on a GPU that
-// holds every workgroup at once each one keeps its tile (and its rows' L2) for
-// the whole solve.  A block is CLAIMED before it runs: tile t's line holds a
-// claim counter beside its done flag, advanced by compare-and-swap, so every
-// task runs exactly once.  An owner claims all its tile's unclaimed blocks
-// with one CAS when it starts (no atomic per block on the fast path).  A
-// workgroup that has waited more than `steal` ticks for a
-// neighbour's block b-1 that nobody has claimed — its owner is not resident
-// (a co-tenant kernel, another model's launch, RCCL kernels, a grid larger
-// than the GPU holds) — claims that block itself, runs it when ready and then
-// returns to its own task (a small stack of claimed tasks in LDS).
-// Deadlock-free by construction: a wait is on a block that is either claimed
-// by a running workgroup or stealable; the owner's own task sits at the
-// bottom of its stack and a thief takes only a block below the one it waits
-// to run (one CAS from the value it read, never "the next one"), so blocks
-// fall strictly up every stack, no task depends on one below it, and waits
-// never form a cycle.  The launch completes with any number of its workgroups resident.
-// (The r3 form needed all of them resident at once: a co-tenant could strand
-// it until its spin limit, with p' left invalid; a ticketed form that took
-// tasks in block order measured 7.6 us per sweep against 4.7: a workgroup
-// then waits for an arbitrary tile's neighbourhood, in effect a grid barrier
-// per block.)
-//
-// Hand-off (MI355X_MICROARCH.md "Valid forms", Consumer, always): p' stores
-// write through (sc1) and every wave drains them (s_waitcnt vmcnt(0)) before
-// the workgroup's barrier, then ONE lane stores the tile's flag (agent scope);
-// a waiting workgroup's wave 0 polls the nine flags (relaxed agent loads,
-// s_sleep), then ONE agent acquire (buffer_inv sc1) + vmcnt(0) + the
-// workgroup barrier before any p' load.  The launch runs several workgroups
-// per CU, outside the table under which sc1 loads alone may replace the
-// acquire, so the acquire stays (acq = 1).  Flags and claim counters hold epoch * 2^kPersistBlockBits
-// + blocks done / claimed (a solve has at most kMaxSweeps / 8 = 512 blocks);
-// the host gives every persistent launch a new epoch (never under graph
-// capture: arguments would freeze), so a value below the epoch's base reads
-// as 0 and nothing needs clearing between launches.  Waits are bounded by
-// wall time (s_memrealtime, `deadline` ticks of 10 ns): past it the waiter
-// sets the abort word persist[1], every workgroup leaves at its next poll or
-// at entry, and a zero-copy host word makes the model's next cfd_* call report
-// CFD_ETIMEOUT (a fault: residency no longer causes one).
-//
-// SUMS guard (r4; sums != 0 when the grid allows the form at all, LdsMarch):
-// task (t, b) of the owner runs the SUMS form when every p' value it reads is
-// below plim = 2^124 / R and every rhs value below rlim = 2^124, which keeps
-// every value its 8 sweeps form below 2^126 / R (a sweep adds at most
-// 0.1875 |rhs| / R to max |p'|: |hz + vt| <= 4 R max|p'| = denom max|p'|), so
-// R |h|, R |v| < 2^127.  What a task reads: rows its 3 x 3 neighbours stored in
-// block b-1 -- each wave publishes max |p'| of its stores with the tile's
-// flag, in the tile's line (words 2-5 / 6-9 by block parity) -- and rows no
-// tile of this launch writes (a slab's rows beyond its band), constant during
-// the launch but different in the two p' buffers: blocks 0 and 1 run the
-// reference's form and measure the tile's inputs in each buffer (and its rhs
-// rows); a stolen task runs the reference's form.  max is NaN-ignoring: a NaN
-// propagates through either form as the same operand.
-constexpr int kStealDepth = 16;
-#ifndef CFD_PERSIST_WPE
-#define CFD_PERSIST_WPE 3   // the padded launch's 3 waves per SIMD: at most 168 VGPRs
-#endif
-template <int T, int FAST>
-__global__ __launch_bounds__(kLdsWaves * 64, CFD_PERSIST_WPE) void k_jacobi_persist(
-    Geom g, float *__restrict__ pa, float *__restrict__ pb, const float *__restrict__ rhs,
-    Ctl *ctl, uint32_t *persist, uint32_t *host_fail, uint32_t *res_slots, uint32_t epoch, int pass,
-    int par0, int nblk, int out_lo, int out_hi, int nwc, int nseg, int wlo, int whi, int ngrp,
-    int acq, uint32_t deadline, uint32_t steal, int late, int sums, float plim, float rlim) {
-    using M = LdsMarch<T, FAST, 4>;
-    __shared__ f2 lds[kLdsWaves * M::D * 64];
-    // control (wave 0 writes, everyone reads after a barrier): the task to
-    // run, the claimed-task stack, the owner's next claimed block
-    // (-2: claim it now, -1: none left)
-    __shared__ int run_tile_s, run_blk_s, abort_s, own_next_s, sp_s, fast_s;
-    __shared__ int stk_tile[kStealDepth], stk_blk[kStealDepth];
-    // the SUMS guard: per-wave maxima of the block just run (lds_block trk),
-    // the own tile's input maxima per p' buffer and its rhs maximum
-    __shared__ float trk_s[3 * kLdsWaves], own_im_s[2], own_rm_s;
-    __shared__ int own_ok_s[2], nfast_s;
-    if (pass_off(ctl, pass)) return;
-    const int ntiles = ngrp * nwc;
-    const int own = xcd_block(g);
-    if (own >= ntiles) return;   // a grid larger than the tiles: nothing owned
-    const unsigned base = epoch << kPersistBlockBits;
-    uint32_t *lines = persist + kPersistHeadLines * kPersistFlagStride;   // per tile: [0] done, [1] claimed
-    const int lane = (int)threadIdx.x & 63;
-    // blocks claimed of a tile from its claim word (values of older epochs read 0)
-    auto count = [&](unsigned v) -> int { return v < base ? 0 : (int)(v - base); };
-    // claim blocks of tile t by CAS from `v` (a read or guess of its claim
-    // word): the first block claimed, or -1 when every block is claimed or
-    // (thief) the word was not `v`.  all = true (the owner, once, when it
-    // starts): every block not yet claimed, retrying from the word's actual
-    // value -- a resident owner thus holds its whole tile and no thief ever
-    // touches it, with no atomic per block.  A thief (all = false) takes
-    // exactly the one block it saw unclaimed, or nothing: a later block of
-    // that tile could depend on a task the thief holds below it on its stack
-    // (a cycle).
-    auto claim = [&](int t, unsigned v, bool all) -> int {
-        uint32_t *w = lines + (size_t)t * kPersistFlagStride + 1;
-        for (;;) {
-            const int c = count(v);
-            if (c >= nblk) return -1;
-            unsigned exp = v;
-            if (__hip_atomic_compare_exchange_strong(w, &exp, base + (unsigned)(all ? nblk : c + 1),
-                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT))
-                return c;
-            if (!all) return -1;
-            v = exp;   // the word as it was: retry from it
-        }
-    };
-    if (threadIdx.x == 0) {
-        sp_s = 0;
-        own_next_s = -2;
-        own_ok_s[0] = own_ok_s[1] = 0;
-        own_im_s[0] = own_im_s[1] = own_rm_s = 0.0f;
-        nfast_s = 0;
-        // fail fast after an abort (every later launch of the model too)
-        abort_s = __hip_atomic_load(persist + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-        if (late > 0 && own % late == 1) {   // test knob: this owner starts late (not resident)
-            const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < 200000u) __builtin_amdgcn_s_sleep(127);
-        }
-    }
-    __syncthreads();
-    if (abort_s) return;
-    for (;;) {
-        if (threadIdx.x < 64) {
-            // ---- wave 0: the next task that is ready (claiming / stealing) ----
-            int sp = sp_s, run_t = -1, run_b = -1;
-            bool fail = false, fast = false;
-            if (sp == 0) {
-                int nb = own_next_s;
-                if (nb == -2) {
-                    int c = -1;
-                    if (lane == 0) c = claim(own, 0u, true);
-                    nb = __builtin_amdgcn_readfirstlane(c);
-                }
-                if (nb >= 0) {
-                    if (lane == 0) {
-                        stk_tile[0] = own;
-                        stk_blk[0] = nb;
-                    }
-                    sp = 1;
-                }
-                own_next_s = -1;
-            }
-            while (sp > 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // stack writes before reads
-                const int tt = stk_tile[sp - 1], bb = stk_blk[sp - 1];
-                if (bb == 0) {
-                    run_t = tt, run_b = bb;
-                    --sp;
-                    break;
-                }
-                // lanes 0..8 watch the task's tile and its neighbours, lane 9 the abort word
-                const int wc = tt % nwc, gi = tt / nwc;
-                const int c = wc + lane % 3 - 1, r = gi + lane / 3 - 1;
-                const bool nbr = lane < 9 && c >= 0 && c < nwc && r >= 0 && r < ngrp;
-                const int nt = nbr ? r * nwc + c : -1;
-                const uint32_t *w = nbr ? lines + (size_t)nt * kPersistFlagStride
-                                        : (lane == 9 ? persist + 1 : nullptr);
-                const unsigned want = base + (unsigned)bb;
-                const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-                bool ready = false, pushed = false;
-                for (;;) {
-                    const unsigned v = w ? __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                         : 0u;
-                    const bool ok = lane < 9 ? (!nbr || v >= want) : v == 0u;
-                    if (__all(ok)) {
-                        ready = true;
-                        break;
-                    }
-                    const uint64_t el = __builtin_amdgcn_s_memrealtime() - t0;
-                    if (__any(lane == 9 && v != 0u) || el > (uint64_t)deadline) {
-                        fail = true;
-                        break;
-                    }
-                    if (el > (uint64_t)steal && sp < kStealDepth) {
-                        // a neighbour block this task needs that nobody has claimed
-                        const unsigned cw = nbr && v < want
-                                                ? __hip_atomic_load(w + 1, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT)
-                                                : 0u;
-                        const bool cand = nbr && v < want && count(cw) < bb;
-                        const uint64_t m = __ballot(cand);
-                        if (m) {
-                            const int l = __builtin_ctzll(m);
-                            const int st = __shfl(nt, l, 64);
-                            const unsigned sv = __shfl(cw, l, 64);
-                            int got = -1;
-                            if (lane == 0) {
-                                got = claim(st, sv, false);
-                                if (got >= 0)   // steals counted for diagnostics (cfd_get_persist_steals)
-                                    __hip_atomic_fetch_add(persist + 2, 1u, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                            got = __builtin_amdgcn_readfirstlane(got);
-                            if (got >= 0) {   // run it first, then come back to this task
-                                if (lane == 0) {
-                                    stk_tile[sp] = st;
-                                    stk_blk[sp] = got;
-                                }
-                                ++sp;
-                                pushed = true;
-                                break;
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                if (fail) break;
-                if (pushed) continue;
-                if (ready) {
-                    run_t = tt, run_b = bb;
-                    --sp;
-                    if (acq) {
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    } else {
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // keeps loads below the poll
-                    }
-                    if (sums && tt == own && bb >= 2 && own_ok_s[bb & 1] && own_rm_s < rlim &&
-                        own_im_s[bb & 1] < plim) {
-                        // the neighbours' stores of block bb-1 (published with their flags)
-                        float mo = 0.0f;
-                        if (nbr) {
-                            const uint32_t *q = w + 2 + 4 * ((bb - 1) & 1);
-#pragma unroll
-                            for (int k = 0; k < kLdsWaves; ++k)
-                                mo = fmaxf(mo, __uint_as_float(__hip_atomic_load(
-                                                   q + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-                        }
-                        fast = wave_max(mo) < plim;
-                    }
-                    break;
-                }
-            }
-            if (lane == 0) {
-                sp_s = sp;
-                run_tile_s = run_t;
-                run_blk_s = run_b;
-                fast_s = fast;
-                abort_s = fail;
-                if (fail) {
-                    __hip_atomic_store(persist + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (host_fail)   // zero-copy host word: cfd_* calls report CFD_ETIMEOUT
-                        __hip_atomic_store(host_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        }
-        __syncthreads();
-        const int tile = run_tile_s, b = run_blk_s;
-        if (abort_s || tile < 0) {   // workgroup-uniform
-            if (threadIdx.x == 0 && nfast_s)   // diagnostics: blocks run in the SUMS form
-                __hip_atomic_fetch_add(persist + 3, (uint32_t)nfast_s, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        const bool fast = fast_s;
-        const bool res = res_slots && b == nblk - 1;   // the solve's last block: its residual too
-#ifndef CFD_PROBE_NOSUMS
-#define CFD_PROBE_NOSUMS 0   // (diagnostic builds: the reference's form only)
-#endif
-        if constexpr (FAST == 1 && !CFD_PROBE_NOSUMS) {
-            if (fast) {
-                if (res)
-                    lds_block<T, FAST, 5, true>(g, pa, pb, rhs, ctl, res_slots, par0 + b, out_lo, out_hi,
-                                                nwc, nseg, wlo, whi, lds, 0, tile, trk_s);
-                else
-                    lds_block<T, FAST, 4, true>(g, pa, pb, rhs, ctl, nullptr, par0 + b, out_lo, out_hi,
-                                                nwc, nseg, wlo, whi, lds, 0, tile, trk_s);
-            }
-        }
-        if (!fast) {
-            if (res)
-                lds_block<T, FAST, 5>(g, pa, pb, rhs, ctl, res_slots, par0 + b, out_lo, out_hi, nwc,
-                                      nseg, wlo, whi, lds, 0, tile, trk_s);
-            else
-                lds_block<T, FAST, 4>(g, pa, pb, rhs, ctl, nullptr, par0 + b, out_lo, out_hi, nwc,
-                                      nseg, wlo, whi, lds, 0, tile, trk_s);
-        }
-        // every wave's max |p'| stored, with (before) the flag: the next
-        // block's guard of the neighbours (written through, drained below)
-        if (sums && lane == 0) {
-            const int wv = (int)threadIdx.x >> 6;
-            __hip_atomic_store(lines + (size_t)tile * kPersistFlagStride + 2 + 4 * (b & 1) + wv,
-                               __float_as_uint(trk_s[3 * wv]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // publish: every wave's write-through stores drained, then one flag
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            // the owner's next block (it claimed all of them when it started)
-            if (tile == own) {
-                own_next_s = b + 1 < nblk ? b + 1 : -1;
-                if (fast) {
-                    ++nfast_s;
-                } else {
-                    // the tile's inputs in the buffer block b read, and its rhs
-                    float im = 0.0f, rm = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < kLdsWaves; ++k) {
-                        im = fmaxf(im, trk_s[3 * k + 1]);
-                        rm = fmaxf(rm, trk_s[3 * k + 2]);
-                    }
-                    own_im_s[b & 1] = fmaxf(own_im_s[b & 1], im);
-                    own_ok_s[b & 1] = 1;
-                    own_rm_s = fmaxf(own_rm_s, rm);
-                }
-            }
-            __hip_atomic_store(lines + (size_t)tile * kPersistFlagStride, base + (unsigned)b + 1u,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-// Workgroups of k_jacobi_lds<T, FAST, RES> one CU holds at once (occupancy
-// API, cached per instantiation).
-// Dynamic LDS added to a launch (bytes) to cap the workgroups the hardware
-// places on one CU, so a round of resident waves is spread evenly at a chosen
-// occupancy.  Default: 24 KiB on fixed-count launches (MODE 0/1) whose p'
-// pair + rhs fit the 256 MiB Infinity Cache: 18 + 24 KiB per 4-wave
-// workgroup admits 3 per CU (3 waves per SIMD) where the registers allow 5,
-// and the round's 3/5 of the waves each march a 5/3 longer segment (less
-// warm-up recompute) on a launch that is VALU- not memory-bound: developed
-// 4096^2 cavity 5.60 -> 5.28 us/sweep (profiles/r3/ab_pad3.log).  None on
-// HBM-streaming slabs, where more waves in flight pay (8192^2: 23.8 vs 24.5
-// us/sweep padded), nor on the speculative launches (ab_pad_parity.log).
-// CFD_LDS_PAD=<bytes> forces one value on every launch.
-// The test is on the OWNED rows (r4): every slab of the weak-scaling series
-// (4096^2, 8192x2048 and 16384x1024, 16.78 M cells, 201 MB) runs the same
-// geometry; with the hg ghost rows counted, the 16384x1024 slab (32 ghost rows
-// each side, 214 MB) fell past the threshold and ran unpadded while the
-// others were padded.  The ghost rows (6 % at C5) still fit the 256 MiB cache.
-inline int lds_pad_bytes(const Geom &g, int mode) {
-    static const int forced = [] {
-        const char *e = getenv("CFD_LDS_PAD");
-        return e ? std::max(0, std::min(64 * 1024, atoi(e))) : -1;
-    }();
-    if (forced >= 0) return forced;
-    constexpr uint64_t kMallResident = 200ull << 20;
-    const uint64_t ws = 3ull * (uint64_t)g.nyl * (uint64_t)g.nx * 4u;
-    return mode <= 1 && ws <= kMallResident ? 24 * 1024 : 0;
-}
+// Workgroups of k_jacobi_lds<T, FAST, MODE> one CU holds at once with `pad`
+// bytes of dynamic LDS (occupancy API, cached per instantiation).
 template <int T, int FAST, int MODE>
 int lds_blocks_per_cu(int pad) {
     static int cache[2] = {0, 0};   // unpadded, padded (one pad value per process)
@@ -1094,76 +719,24 @@ int lds_blocks_per_cu(int pad) {
     return nb;
 }
 
-// Segments per wave column.  g.tb_rows > 0: fixed rows per segment.  0
-// (default): as many segments as ONE round of resident waves holds — every
-// SIMD gets its waves at once and the same march length, so no CU waits for a
-// second, partial round — or whole multiples of a round when a round would
-// make segments longer than kMaxRows.
-// occ_override > 0: size the round for that many workgroups per CU (the
-// persistent kernel's own occupancy)
-template <int T, int FAST, int MODE>
-int lds_segments(const Geom &g, int nrows, int nwc, int pad, int occ_override = 0) {
-    if (g.tb_rows > 0) return cdiv(nrows, g.tb_rows);
-    constexpr int kMaxRows = 160, kMinRows = 8;
-    const int bpc = occ_override > 0 ? occ_override : lds_blocks_per_cu<T, FAST, MODE>(pad);
-    const int wgs_per_col = std::max(1, g.n_cu * bpc / nwc);
-    const int per_round = kLdsWaves * wgs_per_col;
-    // the persistent launch (occ_override) keeps ONE round whatever the
-    // segment length: a tile per resident workgroup, so no tile waits for an
-    // owner that is not resident (8192^2: two rounds made half the tiles run
-    // by stealing, 274 vs 170 us per block, profiles/r4/prof_r4a)
-    const int rounds =
-        occ_override > 0 ? 1 : std::max(1, cdiv(nrows, (long)per_round * kMaxRows));
-    return std::max(1, std::min(per_round * rounds, nrows / kMinRows));
-}
-
-// The grid allows the scaled-sum forms (LdsMarch SUMS): reciprocal multiply,
-// dx^2 == dy^2 with a power-of-two reciprocal R >= 1 (h * R, v * R exact
-// below overflow); CFD_JACOBI_SUMS=0 keeps the reference's form everywhere.
-// Read per launch (one getenv) so tests can change it.
-inline bool lds_sums_grid(const Geom &g) {
-    const char *ue = getenv("CFD_JACOBI_SUMS");
-    int exp2 = 0;
-    const float R = g.r_dx_sq;
-    const bool pow2 = R >= 1.0f && std::frexp(R, &exp2) == 0.5f;
-    return !(ue && atoi(ue) == 0) && g.fastdiv == 1 && g.dx_sq == g.dy_sq && g.r_dx_sq == g.r_dy_sq &&
-           pow2;
-}
-
 template <int T, int MODE>
 void launch_lds_t(const Geom &g, const Fields &f, int pass, int par, int it, int out_lo, int out_hi,
                   uint32_t *rs, hipStream_t s, int lag = 0) {
-    const int nch = g.nx / 2;
-    const int nwc = cdiv(nch, LdsMarch<T, 1, MODE>::OUTL);
-    const int nrows = out_hi - out_lo;
-    const int pad = lds_pad_bytes(g, MODE);
-    const int nseg = g.fastdiv == 1   ? lds_segments<T, 1, MODE>(g, nrows, nwc, pad)
-                     : g.fastdiv == 2 ? lds_segments<T, 2, MODE>(g, nrows, nwc, pad)
-                                      : lds_segments<T, 0, MODE>(g, nrows, nwc, pad);
-    const dim3 grid(nwc * cdiv(nseg, kLdsWaves)), block(kLdsWaves * 64);
+    const int bpc = with_fastdiv(g.fastdiv, [&](auto F) {
+        return lds_blocks_per_cu<T, F(), MODE>(lds_pad_bytes(g, MODE));
+    });
+    const LdsTiles t = lds_tiles(g, T, out_lo, out_hi, MODE, bpc, false);
+    const dim3 grid(t.nwc * cdiv(t.nseg, kLdsWaves)), block(kLdsWaves * 64);
     float *pa = f.pp[0] - (long)g.hg * g.nx, *pb = f.pp[1] - (long)g.hg * g.nx;
-    // a segment whose rows reach a global boundary row runs the kCol|kRow
-    // path, ~1.45x the VALU work per row of an interior one (r2 wave
-    // timeline): it gets ~1/1.45 of the rows
-    constexpr int kEdgeWeight = 11;
-    const int reach = T + 2;
-    const int wlo = out_lo - reach <= 1 - g.j0 ? kEdgeWeight : 16;
-    const int whi = out_hi + reach >= g.ny - 2 - g.j0 ? kEdgeWeight : 16;
     // the fma form's guard constant (k_jacobi_lds): fixed-count launches of
     // one domain (a slab's bound would need its neighbours' maxima) on a grid
     // that allows the form; the sweeps of a solve are at most kMaxSweeps
     const float sums_c =
         MODE <= 1 && g.j0 == 0 && g.nyl == g.ny && lds_sums_grid(g) ? 0.1875f * kMaxSweeps : 0.0f;
-#define CFD_LDS_LAUNCH(FASTV)                                                                     \
-    hipLaunchKernelGGL((k_jacobi_lds<T, FASTV, MODE>), grid, block, pad, s, g, pa, pb, f.rhs, f.ctl, \
-                       rs, pass, par, out_lo, out_hi, nwc, nseg, wlo, whi, it, lag, sums_c)
-    if (g.fastdiv == 1)
-        CFD_LDS_LAUNCH(1);
-    else if (g.fastdiv == 2)
-        CFD_LDS_LAUNCH(2);
-    else
-        CFD_LDS_LAUNCH(0);
-#undef CFD_LDS_LAUNCH
+    with_fastdiv(g.fastdiv, [&](auto F) {
+        hipLaunchKernelGGL((k_jacobi_lds<T, F(), MODE>), grid, block, t.pad, s, g, pa, pb, f.rhs, f.ctl,
+                           rs, pass, par, out_lo, out_hi, t.nwc, t.nseg, t.wlo, t.whi, it, lag, sums_c);
+    });
 }
 
 // T sweeps per launch: mode 0 / 1 (plain / last-stage residual, chosen by
@@ -1187,105 +760,5 @@ void launch_lds_T(const Geom &g, const Fields &f, int pass, int par, int it, int
         launch_lds_t<T, 0>(g, f, pass, par, it, out_lo, out_hi, rs, s);
 }
 
-// Workgroups of k_jacobi_persist<T, FAST> one CU holds at once with `pad`
-// bytes of dynamic LDS: the occupancy API on the launched kernel itself,
-// capped by the SGPR rule of MI355X_MICROARCH.md (Residency): at 97-112 SGPRs
-// the hardware admits 6 four-wave workgroups where the API may say 7.  Used to
-// size the tiles so one round of workgroups covers them; residency is no
-// longer a correctness condition (claims and stealing, k_jacobi_persist).
-template <int T, int FAST>
-int persist_blocks_per_cu(int pad) {
-    static int cache[2] = {0, 0};
-    int &nb = cache[pad > 0 ? 1 : 0];
-    if (nb == 0) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &n, reinterpret_cast<const void *>(&k_jacobi_persist<T, FAST>), kLdsWaves * 64, pad) !=
-                hipSuccess ||
-            n < 1)
-            n = 1;
-        nb = std::min(n, 6);
-    }
-    return nb;
-}
-
-// The persistent form of launch_lds_t<T, 0> over nblk blocks: the same tile
-// geometry (pad, segments, weights), its round sized by the persistent
-// kernel's own occupancy; one workgroup per tile.  false (nothing launched):
-// more tiles than kPersistMaxGroups lines, or row groups shorter than two
-// T-row bands.
-template <int T>
-bool launch_lds_persist_t(const Geom &g, const Fields &f, int pass, int par0, int nblk, int out_lo,
-                          int out_hi, uint32_t epoch, uint32_t *rs, hipStream_t s) {
-    const int nch = g.nx / 2;
-    const int nwc = cdiv(nch, LdsMarch<T, 1, 0>::OUTL);
-    const int nrows = out_hi - out_lo;
-    const int pad = lds_pad_bytes(g, 0);
-    const int occ = g.fastdiv == 1   ? persist_blocks_per_cu<T, 1>(pad)
-                    : g.fastdiv == 2 ? persist_blocks_per_cu<T, 2>(pad)
-                                     : persist_blocks_per_cu<T, 0>(pad);
-    const int nseg = g.fastdiv == 1   ? lds_segments<T, 1, 0>(g, nrows, nwc, pad, occ)
-                     : g.fastdiv == 2 ? lds_segments<T, 2, 0>(g, nrows, nwc, pad, occ)
-                                      : lds_segments<T, 0, 0>(g, nrows, nwc, pad, occ);
-    const int ngrp = cdiv(nseg, kLdsWaves);
-    // rows for a T-row band per group: a task's input rows lie in its 3 x 3
-    // neighbourhood
-    if (ngrp * nwc > kPersistMaxGroups || nrows < ngrp * 2 * T) return false;
-    // one workgroup per tile (each owns one); CFD_PERSIST_GRID=<n> launches
-    // n >= tiles (the surplus owns nothing and leaves).  Knobs are read per
-    // launch (one getenv each per solve) so tests can change them.
-    const char *ge = getenv("CFD_PERSIST_GRID");
-    const int nwg = std::max(ngrp * nwc, ge ? atoi(ge) : 0);
-    const dim3 grid(nwg), block(kLdsWaves * 64);
-    float *pa = f.pp[0] - (long)g.hg * g.nx, *pb = f.pp[1] - (long)g.hg * g.nx;
-    constexpr int kEdgeWeight = 11;
-    const int reach = T + 2;
-    const int wlo = out_lo - reach <= 1 - g.j0 ? kEdgeWeight : 16;
-    const int whi = out_hi + reach >= g.ny - 2 - g.j0 ? kEdgeWeight : 16;
-    const int acq = 1;   // the agent acquire after each poll (MI355X_MICROARCH.md)
-    // wait deadline in s_memrealtime ticks (100 MHz): CFD_PERSIST_DEADLINE_US,
-    // default 10 s (a wait that long is a fault; time-sliced GPUs stay far
-    // below it)
-    const char *de = getenv("CFD_PERSIST_DEADLINE_US");
-    const double dl_us = de ? std::max(0.0, atof(de)) : 10e6;
-    const uint32_t deadline = (uint32_t)std::min(4.0e9, dl_us * 100.0);
-    // a neighbour block unclaimed after this long is stolen
-    // (CFD_PERSIST_STEAL_US, default 50 us: a block takes ~40 us at 4096^2)
-    const char *se = getenv("CFD_PERSIST_STEAL_US");
-    const double st_us = se ? std::max(0.0, atof(se)) : 50.0;
-    const uint32_t steal = (uint32_t)std::min(4.0e9, st_us * 100.0);
-    // test knob: owners of tiles w % k == 1 start 2 ms late (CFD_PERSIST_LATE=k)
-    const char *le = getenv("CFD_PERSIST_LATE");
-    const int late = le ? std::max(0, atoi(le)) : 0;
-    // the SUMS form (LdsMarch): reciprocal multiply, dx^2 == dy^2 with a
-    // power-of-two reciprocal R >= 1 (h * R, v * R exact below overflow);
-    // CFD_JACOBI_SUMS=0 keeps the reference's form everywhere
-    const float R = g.r_dx_sq;
-    const int sums = lds_sums_grid(g);
-    const float plim = sums ? std::ldexp(1.0f, 124) / R : 0.0f, rlim = std::ldexp(1.0f, 124);
-#define CFD_LDS_PLAUNCH(FASTV)                                                                     \
-    hipLaunchKernelGGL((k_jacobi_persist<T, FASTV>), grid, block, pad, s, g, pa, pb, f.rhs, f.ctl, \
-                       f.persist, f.host_nonfinite ? f.host_nonfinite + 2 : nullptr, rs, epoch, pass, \
-                       par0, nblk, out_lo, out_hi, nwc, nseg, wlo, whi, ngrp, acq, deadline, steal,  \
-                       late, sums, plim, rlim)
-    if (g.fastdiv == 1)
-        CFD_LDS_PLAUNCH(1);
-    else if (g.fastdiv == 2)
-        CFD_LDS_PLAUNCH(2);
-    else
-        CFD_LDS_PLAUNCH(0);
-#undef CFD_LDS_PLAUNCH
-    return true;
-}
-
 }  // namespace
-
-// per-translation-unit entry points (cfd_jacobi_lds*.hip)
-void launch_lds_t567(const Geom &g, const Fields &f, int T, int pass, int par, int it, int out_lo,
-                     int out_hi, uint32_t *rs, int mode, hipStream_t s, int lag);
-void launch_lds_t8(const Geom &g, const Fields &f, int pass, int par, int it, int out_lo, int out_hi,
-                   uint32_t *rs, int mode, hipStream_t s, int lag);
-bool launch_lds_persist8(const Geom &g, const Fields &f, int pass, int par0, int nblk, int out_lo,
-                         int out_hi, uint32_t epoch, uint32_t *rs, hipStream_t s);
-
 }  // namespace cfd

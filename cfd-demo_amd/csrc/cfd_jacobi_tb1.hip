@@ -267,15 +267,10 @@ void launch_t(const Geom &g, const Fields &f, int pass, int it, int par, int out
     }
     const dim3 grid(nwc * cdiv(nseg, kJacWavesPerBlock)), block(kJacWavesPerBlock * 64);
     float *pa = f.pp[0] - (long)g.hg * g.nx, *pb = f.pp[1] - (long)g.hg * g.nx;
-    if (g.fastdiv == 1)
-        hipLaunchKernelGGL((k_jacobi_tb<T, 1>), grid, block, 0, s, g, pa, pb, f.rhs, f.ctl, rs,
+    with_fastdiv(g.fastdiv, [&](auto F) {
+        hipLaunchKernelGGL((k_jacobi_tb<T, F()>), grid, block, 0, s, g, pa, pb, f.rhs, f.ctl, rs,
                            pass, it, par, out_lo, out_hi, nwc, nseg);
-    else if (g.fastdiv == 2)
-        hipLaunchKernelGGL((k_jacobi_tb<T, 2>), grid, block, 0, s, g, pa, pb, f.rhs, f.ctl, rs,
-                           pass, it, par, out_lo, out_hi, nwc, nseg);
-    else
-        hipLaunchKernelGGL((k_jacobi_tb<T, 0>), grid, block, 0, s, g, pa, pb, f.rhs, f.ctl, rs,
-                           pass, it, par, out_lo, out_hi, nwc, nseg);
+    });
 }
 
 }  // namespace

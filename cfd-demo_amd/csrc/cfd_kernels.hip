@@ -770,15 +770,10 @@ void launch_jacobi_sweep(const Geom &g, const Fields &f, int pass, int it, int r
     const int nseg = cdiv(row_hi - row_lo, kJacRowsPerWave);
     float *pa = f.pp[0] - (long)g.hg * g.nx, *pb = f.pp[1] - (long)g.hg * g.nx;
     const dim3 grid(nbx * nseg), block(kJacWavesPerBlock * 64);
-    if (g.fastdiv == 1)
-        hipLaunchKernelGGL((k_jacobi<kJacRowsPerWave, 1>), grid, block, 0, s, g, pa, pb, f.rhs,
+    with_fastdiv(g.fastdiv, [&](auto F) {
+        hipLaunchKernelGGL((k_jacobi<kJacRowsPerWave, F()>), grid, block, 0, s, g, pa, pb, f.rhs,
                            f.ctl, f.err_slots, pass, it, row_lo, row_hi, nbx, res);
-    else if (g.fastdiv == 2)
-        hipLaunchKernelGGL((k_jacobi<kJacRowsPerWave, 2>), grid, block, 0, s, g, pa, pb, f.rhs,
-                           f.ctl, f.err_slots, pass, it, row_lo, row_hi, nbx, res);
-    else
-        hipLaunchKernelGGL((k_jacobi<kJacRowsPerWave, 0>), grid, block, 0, s, g, pa, pb, f.rhs,
-                           f.ctl, f.err_slots, pass, it, row_lo, row_hi, nbx, res);
+    });
 }
 
 void launch_jacobi_block(const Geom &g, const Fields &f, int pass, int it, int par, int T,

@@ -263,7 +263,7 @@ int build_model(cfd_model *m, const cfd_grid *grid, const cfd_params *p, int dev
     m->t_max = std::min(m->t_max, g.tb_kind == 1 ? 4 : kMaxTemporal);
     // output rows per wave segment: 24 for kind 4 (12-slot unrolled march);
     // kind 5 sizes its segments to one round of resident waves (tb_rows 0,
-    // cfd_jacobi_lds.hip lds_segments; 4096^2: ~38 rows, fixed 40 rows gave
+    // cfd_jacobi_lds.hip lds_tiles; 4096^2: ~38 rows, fixed 40 rows gave
     // 6.42 us/sweep, 32 gave 6.50, 24 gave 6.68)
     g.tb_rows = g.tb_kind == 5 ? 0 : 24;
     if (opt.tb_rows != kEnvUnset) g.tb_rows = std::max(4, std::min(1024, opt.tb_rows));

@@ -4,6 +4,9 @@
 # T = 8 launch), for A/B runs on the GPU:
 #   CFD_LIB=cfd-demo_amd/lib/variants/<name>/libcfd_amd.so python tools/tb_one.py
 # Usage: [VARIANT_TU=cfd_jacobi_lds567] tools/build_variants.sh name:"-DFLAG=1 -DOTHER=2" ...
+# The kind-5 knobs are the block at the top of csrc/cfd_jacobi_lds.h, e.g.
+#   tools/build_variants.sh pd4:"-DCFD_LDS_PD=4" stamp:"-DCFD_LDS_STAMP=1"
+# (VARIANT_TU=cfd_jacobi_lds_persist for CFD_PERSIST_WPE).
 set -e
 cd "$(dirname "$0")/../cfd-demo_amd"
 make -s -j8
