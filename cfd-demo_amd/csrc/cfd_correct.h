@@ -1,6 +1,7 @@
 // cfd_correct.h — the reference's corrector arithmetic (apply_corrector,
 // model.rs:1334-1404) and the publications that end a corrector launch, shared
-// by the corrector kernels (cfd_correct.hip).  Each helper keeps the
+// by the corrector kernels (cfd_correct.hip) and the fused finish of the
+// predictor march (cfd_predict_march.hip).  Each helper keeps the
 // reference's evaluation order, so every kernel that calls it stores the same
 // bits.  The divergence of a pass head is div4 (cfd_device.h).
 #pragma once
@@ -33,6 +34,21 @@ __device__ __forceinline__ void v_corr4(const Geom &g, const float4 &vs, const f
     o.y = v_corr<SP>(g, vs.y, pt.y, pb.y, dt);
     o.z = v_corr<SP>(g, vs.z, pt.z, pb.z, dt);
     o.w = v_corr<SP>(g, vs.w, pt.w, pb.w, dt);
+}
+
+// Final u face value at (i, j) of the corrector finish, from its operands:
+// ustar = u_star at the face (u_star of face nx-1 for the outflow face nx),
+// p_right / p_left = the p' cells either side (p'(nx-1), p'(nx-2) for face nx:
+// the outflow copies the corrected face nx-1, whose form is the Q9 tail's).
+template <int SP>
+__device__ __forceinline__ float cf_u_face(const Geom &g, float inlet, float dt, int i, int j,
+                                           float ustar, float p_right, float p_left) {
+    const int nx = g.nx;
+    if (j == 0) return 0.0f;
+    if (j == g.ny - 1) return (g.bc_kind == 1 && i > 0 && i < nx) ? inlet : 0.0f;
+    if (i == 0) return g.bc_kind == 0 ? inlet_value(g, inlet, j) : 0.0f;
+    if (i == nx) return g.bc_kind == 0 ? u_corr<SP>(g, ustar, p_right, p_left, dt, nx) : 0.0f;
+    return u_corr<SP>(g, ustar, p_right, p_left, dt, i);
 }
 
 // p += p' (model.rs:1392-1403)

@@ -272,21 +272,6 @@ __global__ __launch_bounds__(kBlock) void k_correct_head4(Geom g, Fields f, int 
 
 // ------------------------------- fused corrector + boundaries + reductions (K5')
 
-// Final u face value at (i, j) of the corrector finish, from its operands:
-// ustar = u_star at the face (u_star of face nx-1 for the outflow face nx),
-// p_right / p_left = the p' cells either side (p'(nx-1), p'(nx-2) for face nx:
-// the outflow copies the corrected face nx-1, whose form is the Q9 tail's).
-template <int SP>
-__device__ __forceinline__ float cf_u_face(const Geom &g, float inlet, float dt, int i, int j,
-                                           float ustar, float p_right, float p_left) {
-    const int nx = g.nx;
-    if (j == 0) return 0.0f;
-    if (j == g.ny - 1) return (g.bc_kind == 1 && i > 0 && i < nx) ? inlet : 0.0f;
-    if (i == 0) return g.bc_kind == 0 ? inlet_value(g, inlet, j) : 0.0f;
-    if (i == nx) return g.bc_kind == 0 ? u_corr<SP>(g, ustar, p_right, p_left, dt, nx) : 0.0f;
-    return u_corr<SP>(g, ustar, p_right, p_left, dt, i);
-}
-
 // One row of k_correct_finish4m's work for the 4 columns i0..i0+3 of local
 // row lj: pc = p' row lj, pb = p' row lj-1 (loaded by the caller), the step
 // maxima and the non-finite flag accumulate into du..bad.

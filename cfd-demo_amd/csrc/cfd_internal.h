@@ -121,6 +121,9 @@ struct Ctl {
     // 2, 4 and 5): the residual of the last iteration run, whose f32 rounding
     // is last_p.  Written by k_publish_f64 behind the solve's finalize.
     double last_p64;
+    // dt of the last uv-fused step (k_predict_march MODE 2), for the launch
+    // that materialises its u*, v* on demand (cfd_model::need_star)
+    float star_dt;
 };
 
 // The double residual's spread maxima (cfd_script_options.residual_f64): a
@@ -216,13 +219,21 @@ void launch_predict(const Geom &g, const Fields &f, float dt_override, bool vec,
 // both schemes' predictors + divergence in one row march (cfd_predict_march.hip),
 // when predict_march_ok(): replaces launch_predict + the step's first divergence
 bool predict_march_ok(const Geom &g, const Fields &f);
+int predict_march_workgroups(const Geom &g);
 // set_inlet: also set Ctl::inlet from Ctl::step (k_step_begin's ramp,
 // model.rs:311-316) — the step's k_step_begin is then not launched
 // [row_lo, row_hi): the divergence rows the launch forms (>= 4 rows; default
 // all owned rows) — a sharded step runs rows [2, nyl-2), which read no u/v
 // ghost row, while the ghost exchange is in flight
+// mode (the uv-fused fixed-count step, cfd_options::uv_fused; one domain,
+// all owned rows): 1 stores rhs only; 2 is the corrector finish on the same
+// march after the solve -- it forms u*, v* again from f.u / f.v and stores the
+// new u, v into f.u_old / f.v_old (the caller then swaps the pairs), p += p',
+// the step maxima, Ctl::star_dt.  star (mode 0): f.u / f.v are that step's old
+// pair; store the u*, v* it never stored (dt = Ctl::star_dt), rhs stays.
 void launch_predict_march(const Geom &g, const Fields &f, float dt_override, hipStream_t s,
-                          bool set_inlet = false, int row_lo = 0, int row_hi = -1);
+                          bool set_inlet = false, int row_lo = 0, int row_hi = -1, int mode = 0,
+                          bool star = false);
 void launch_divergence(const Geom &g, const Fields &f, int pass, float dt_override,
                        hipStream_t s);
 // One Jacobi sweep over local rows [row_lo, row_hi) (may reach into ghosts).

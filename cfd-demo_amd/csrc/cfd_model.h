@@ -160,6 +160,7 @@ struct cfd_options {
     bool graph = false;            // CFD_GRAPH (0): cfd_update_n replays a captured hipGraph of graph_steps steps
     bool ckpt = true;              // CFD_CKPT (1): self-recovery checkpoint; 0: a solve timeout invalidates the state
     int fastdiv = cfd::kEnvUnset;       // CFD_FASTDIV (unset: cheapest proven form): 0 IEEE division, 2 prefer the FMA-corrected form
+    int uv_fused = cfd::kEnvUnset;      // CFD_UV_FUSED (unset: first order on a grid that fills the chip): the fixed-count step on one domain keeps u*, v* out of memory (uv_fused_ok); 1 wherever it applies, 0 never
     int resident_div = cfd::kEnvUnset;  // CFD_RESIDENT_DIV (unset): 3 lets the resident solve take the guarded FMA form
     int pred_div = cfd::kEnvUnset;      // CFD_PRED_DIV (unset: 2): 0 IEEE division in the predictors
     int tb_kind = cfd::kEnvUnset;       // CFD_TB_KIND (unset: 5 with the exact reciprocal, else 4): 1, 4 or 5
@@ -267,6 +268,14 @@ struct cfd_model {
     bool stepped = false;    // ev_step0 / ev_step1 hold a step
     hipGraphExec_t step_graph = nullptr;
     int graph_cur_delta = 0;   // host_cur advance of one replay
+    // the uv-fused step (cfd_options::uv_fused): its finish stores the new
+    // u, v into the u_old / v_old arrays and the host swaps the pairs in
+    // Fields, so f.u / f.v are always the current fields and f.u_old / f.v_old
+    // the step's old ones.  uv_flip: the pairs are swapped against the
+    // allocation order; star_lazy: the last step stored no u*, v* (need_star
+    // materialises them from the old pair before anything reads them)
+    int uv_flip = 0, graph_uv_flip = 0, graph_uv_delta = 0, ck_uv_flip = 0;
+    bool star_lazy = false, ck_star_lazy = false;
     int graph_steps = 4;
     // self-recovery checkpoint (ck_begin)
     struct CkSeg {
@@ -415,6 +424,9 @@ struct cfd_model {
     void pass_head(int pass, float dt_override);
     int enqueue_piso(float dt_override, bool finish = false);
     int enqueue_update(bool rec_step = true);
+    bool uv_fused_ok() const;
+    void swap_uv();
+    int need_star();
     bool graph_ok() const;
     void drop_graph();
     int update_graph(int n);

@@ -161,6 +161,7 @@ int cfd_update_n(cfd_model *m, int n) {
 int cfd_piso_step(cfd_model *m, float dt_sub) {
     if (!m) return fail(CFD_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->need_star()) return rc;
     if (int rc = m->invalidate_sums()) return rc;
     if (int rc = m->ck_begin()) return rc;
     auto run = [m, dt_sub]() {
@@ -198,6 +199,7 @@ int cfd_pressure_solve(cfd_model *m, float *residual_out) {
 int cfd_run_phase(cfd_model *m, int phase, float dt_sub) {
     if (!m) return fail(CFD_EINVAL, "null model");
     HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->need_star()) return rc;
     if (int rc = m->invalidate_sums()) return rc;
     switch (phase) {
     case CFD_PHASE_U_PREDICTOR: {
@@ -226,6 +228,8 @@ int cfd_set_params(cfd_model *m, const cfd_params *p) {
     int rc = validate(&m->grid, p);
     if (rc) return rc;
     rc = validate_sharded(m, p);
+    if (rc) return rc;
+    rc = m->need_star();   // with the parameters the step ran under
     if (rc) return rc;
     rc = m->sync();
     if (rc) return rc;
@@ -347,7 +351,9 @@ int cfd_get_residuals(cfd_model *m, cfd_residuals *out) {
 int cfd_get_state(cfd_model *m, cfd_state *st) {
     if (!m || !st) return fail(CFD_EINVAL, "null argument");
     Ctl c;
-    int rc = m->read_ctl(&c);
+    int rc = m->need_star();
+    if (rc) return rc;
+    rc = m->read_ctl(&c);
     if (rc) return rc;
     const size_t W = (size_t)m->g.nx + 1, nx = (size_t)m->g.nx, nyl = (size_t)m->g.nyl;
     if (st->u) HIP_TRY(hipMemcpy(st->u, m->f.u, nyl * W * 4, hipMemcpyDeviceToHost));
@@ -370,7 +376,9 @@ int cfd_get_state(cfd_model *m, cfd_state *st) {
 int cfd_set_state(cfd_model *m, const cfd_state *st) {
     if (!m || !st) return fail(CFD_EINVAL, "null argument");
     Ctl c;
-    int rc = m->read_ctl(&c);
+    int rc = m->need_star();   // the fields the caller leaves out keep their values
+    if (rc) return rc;
+    rc = m->read_ctl(&c);
     if (rc) return rc;
     const size_t W = (size_t)m->g.nx + 1, nx = (size_t)m->g.nx, nyl = (size_t)m->g.nyl;
     if (st->u) HIP_TRY(hipMemcpy(m->f.u, st->u, nyl * W * 4, hipMemcpyHostToDevice));

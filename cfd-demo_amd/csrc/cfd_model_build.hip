@@ -26,6 +26,7 @@ cfd_options read_options() {
     o.pred_vec = env_flag("CFD_PRED_VEC", true);
     o.corr_vec = env_flag("CFD_CORR_VEC", true);
     o.corr_head = env_flag("CFD_CORR_HEAD", true);
+    o.uv_fused = env_int("CFD_UV_FUSED", kEnvUnset);
     o.graph = env_flag("CFD_GRAPH", false);
     o.ckpt = env_flag("CFD_CKPT", true);
     o.fastdiv = env_int("CFD_FASTDIV", kEnvUnset);

@@ -306,6 +306,7 @@ int script_check(cfd_model *m, const cfd_script_step *s) {
 // of cfd_script_update
 int cfd_model::script_substep(const cfd_script_step *s) {
     HIP_TRY(hipSetDevice(device));
+    if (int rc = need_star()) return rc;
     if (int rc = invalidate_sums()) return rc;
     if (int rc = ck_begin()) return rc;
     cfd_model *m = this;
@@ -336,6 +337,7 @@ int cfd_script_phase(cfd_model *m, int phase, const cfd_script_step *s) {
     if (phase != CFD_SCRIPT_PHASE_PREDICT && phase != CFD_SCRIPT_PHASE_CORRECT)
         return fail(CFD_EINVAL, "unknown script phase");
     HIP_TRY(hipSetDevice(m->device));
+    if (int rc = m->need_star()) return rc;
     if (int rc = m->invalidate_sums()) return rc;
     ScriptStep k;
     if (int rc = m->script_prepare(s, &k)) return rc;

@@ -55,13 +55,70 @@ void cfd_model::pass_head(int pass, float dt_override) {
     }
 }
 
+// The uv-fused step applies: one domain, a Jacobi solve, the predictor march.
+// By default only where it was measured against the step it replaces (DESIGN
+// §5 r11): the first-order scheme on a grid whose march has at least 4
+// workgroups per CU (4096^2: 8.5).  The second-order finish (4-row segments,
+// two waves per SIMD) and small grids, where the march's few fat workgroups
+// replace k_correct_finish4m's one-row bands, run it only with CFD_UV_FUSED=1.
+bool cfd_model::uv_fused_ok() const {
+    if (opt.uv_fused == 0 || sharded() || host_driven() ||
+        params.pressure_solver != CFD_SOLVER_JACOBI || !predict_march_ok(g, f))
+        return false;
+    if (opt.uv_fused != kEnvUnset) return true;
+    return g.scheme == 0 && predict_march_workgroups(g) >= 4 * g.n_cu;
+}
+void cfd_model::swap_uv() {
+    std::swap(f.u, f.u_old);
+    std::swap(f.v, f.v_old);
+    std::swap(f.u_alloc_base, f.u_old_base);
+    std::swap(f.v_alloc_base, f.v_old_base);
+    uv_flip ^= 1;
+}
+// u*, v* of the last uv-fused step, which stored none: the storing march over
+// that step's old u, v (f.u_old / f.v_old since the swap) with its dt
+// (Ctl::star_dt) -- the values the step formed in registers, bit for bit.
+// Called before anything outside a uv-fused step reads or writes u*, v*.
+int cfd_model::need_star() {
+    if (!star_lazy) return 0;
+    HIP_TRY(hipSetDevice(device));
+    Fields fm = f;
+    fm.u = f.u_old;
+    fm.v = f.v_old;
+    fm.u_alloc_base = f.u_old_base;
+    fm.v_alloc_base = f.v_old_base;
+    fm.sums_track = 0;
+    launch_predict_march(g, fm, kNaN, stream, false, 0, -1, 0, true);
+    HIP_TRY(hipGetLastError());
+    star_lazy = false;
+    return 0;
+}
+
 // piso_step (model.rs:529-730).
 // finish = inside update() with no extra corrector passes: the corrector,
 // the boundaries and the step reductions run as one fused pass.
 int cfd_model::enqueue_piso(float dt_override, bool finish) {
     // K1-K3: the fused march when it applies, else predictors + divergence
     const bool march = predict_march_ok(g, f);
+    // the fixed-count step that keeps u*, v* out of memory: the march stores
+    // rhs only, and the finish forms u*, v* again from the old u, v it reads
+    // anyway and stores the new u, v into the other pair of arrays
+    const bool uvf = finish && uv_fused_ok();
+    if (!uvf)
+        if (int rc = need_star()) return rc;
     phase_mark(0, false);
+    if (uvf) {
+        launch_predict_march(g, f, dt_override, stream, step_begin_folded, 0, -1, 1);
+        phase_mark(0, true);
+        if (int rc = enqueue_solve(0)) return rc;
+        phase_mark(1, false);
+        launch_predict_march(g, f, dt_override, stream, false, 0, -1, 2);
+        phase_mark(1, true);
+        HIP_TRY(hipGetLastError());
+        swap_uv();
+        star_lazy = true;
+        return 0;
+    }
     if (march && finish && uv_async) {
         // rows [2, nyl-2) read u rows >= 0 and <= nyl-1 and v rows <= nyl;
         // the edge rows (4-row launches overlapping the interior ones:
@@ -206,7 +263,8 @@ void cfd_model::drop_graph() {
 }
 int cfd_model::update_graph(int n) {
     if (!step_graph) {
-        const int hc0 = host_cur;
+        const int hc0 = host_cur, fl0 = uv_flip;
+        const bool sl0 = star_lazy;
         HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
         int rc = 0;
         capturing = true;
@@ -217,6 +275,8 @@ int cfd_model::update_graph(int n) {
         if (rc || ce != hipSuccess) {
             if (graph) (void)hipGraphDestroy(graph);
             host_cur = hc0;
+            if (uv_flip != fl0) swap_uv();
+            star_lazy = sl0;
             return rc ? rc : fail(CFD_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
         }
         const hipError_t ie = hipGraphInstantiate(&step_graph, graph, nullptr, nullptr, 0);
@@ -224,15 +284,30 @@ int cfd_model::update_graph(int n) {
         if (ie != hipSuccess) {
             step_graph = nullptr;
             host_cur = hc0;
+            if (uv_flip != fl0) swap_uv();
+            star_lazy = sl0;
             return fail(CFD_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
         }
         graph_cur_delta = (host_cur - hc0) & 1;
         host_cur = hc0;   // captured, not executed
+        // the captured kernels hold the u / v pairs as they were at the
+        // capture's first step: a replay starts from that arrangement
+        graph_uv_flip = fl0;
+        graph_uv_delta = uv_flip ^ fl0;
+        if (uv_flip != fl0) swap_uv();
+        star_lazy = sl0;
     }
     int k = 0;
-    for (; k + graph_steps <= n - 1; k += graph_steps) {   // the last step stays out: it
-        HIP_TRY(hipGraphLaunch(step_graph, stream));       // records the step time
+    if (uv_flip != graph_uv_flip && n > 1) {   // a plain step brings the pairs back
+        int rc = enqueue_update(false);
+        if (rc) return rc;
+        k = 1;
+    }
+    for (; uv_flip == graph_uv_flip && k + graph_steps <= n - 1; k += graph_steps) {
+        HIP_TRY(hipGraphLaunch(step_graph, stream));       // the last step stays out: it records the step time
         host_cur = (host_cur + graph_cur_delta) & 1;
+        if (graph_uv_delta) swap_uv();
+        if (uv_fused_ok() && params.corrector_passes == 0) star_lazy = true;
     }
     for (; k < n; ++k) {
         int rc = enqueue_update(k == n - 1);
@@ -334,6 +409,8 @@ int cfd_model::ck_begin() {
     }
     ck_host_cur = host_cur;
     ck_shallow = pp_ghosts_shallow;
+    ck_uv_flip = uv_flip;
+    ck_star_lazy = star_lazy;
     ck_replay.clear();
     ck_open = true;
     return 0;
@@ -374,6 +451,8 @@ int cfd_model::recover() {
     *(volatile uint32_t *)h_nonfinite = 0u;
     host_cur = ck_host_cur;
     pp_ghosts_shallow = ck_shallow;
+    if (uv_flip != ck_uv_flip) swap_uv();
+    star_lazy = ck_star_lazy;
     ++recoveries;
     std::vector<std::function<int()>> replay;
     replay.swap(ck_replay);
