@@ -34,6 +34,8 @@ EXPORTS = [
     "cfd_mesh_from_quadtree", "cfd_mesh_sizes", "cfd_mesh_cells", "cfd_mesh_neighbors",
     "cfd_mesh_intersections", "cfd_mesh_full_bounding_box", "cfd_mesh_build_ms",
     "cfd_mesh_destroy",
+    "cfd_raster_polygon", "cfd_raster_quadtree", "cfd_raster_mesh", "cfd_raster_mesh_view",
+    "cfd_mesh_view_size",
     "cfd_tracers_enable", "cfd_tracers_disable", "cfd_tracers_count", "cfd_tracers_get",
     "cfd_tracers_set", "cfd_tracers_advance", "cfd_tracers_inject", "cfd_tracers_density",
     "cfd_run_set_tracers", "cfd_run_last_tracers",
@@ -238,6 +240,16 @@ def load():
         "cfd_mesh_full_bounding_box": (i32, [vp, C.POINTER(CfdAabb)]),
         "cfd_mesh_build_ms": (i32, [vp, C.POINTER(C.c_double)]),
         "cfd_mesh_destroy": (None, [vp]),
+        # Mesh tab images
+        "cfd_raster_polygon": (i32, [vp, i32, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), DP]),
+        "cfd_raster_quadtree": (i32, [vp, C.POINTER(CfdAabb), i32, C.c_size_t, C.c_size_t,
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), DP]),
+        "cfd_raster_mesh": (i32, [vp, C.POINTER(CfdAabb), i32, C.c_size_t, C.c_size_t,
+                                  C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), DP]),
+        "cfd_raster_mesh_view": (i32, [vp, vp, i32, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8),
+                                       DP]),
+        "cfd_mesh_view_size": (i32, [C.POINTER(CfdAabb), f32, f32, C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t)]),
         # tracer particles
         "cfd_script_piso_step": (i32, [vp, C.POINTER(CfdScriptStep)]),
         "cfd_script_phase": (i32, [vp, i32, C.POINTER(CfdScriptStep)]),

@@ -14,9 +14,16 @@ Names follow the reference:
     tesselate -> QuadTree                         quad_tree.rs:17-100
     Mesh.from_quad_tree (on the GPU),
       visit_cell, full_bounding_box               mesh.rs:51-338
+    rasterize_polygon                             utils/polygon_rasterizer.rs:22-103
+    rasterize_quad_tree                           utils/quad_tree_rasterizer.rs:6-59
+    rasterize_mesh, rasterize_mesh_no_background  utils/mesh_rasterizer.rs:8-57
+    mesh_view_image, mesh_view_size               views/mesh_view.rs:75-94
 
 Geometry and tesselation run on the host; Mesh.from_quad_tree runs its
-leaf filter, O(n^2) neighbour search and intersections as HIP kernels.
+leaf filter, O(n^2) neighbour search and intersections as HIP kernels, and
+the rasterisers draw on the GPU (csrc/cfd_mesh_raster.hip): each returns an
+(h, w, 4) uint8 RGBA image, row 0 the reference's y = 0, and leaves the
+device time of its kernels in the module attribute last_raster_ms.
 """
 from __future__ import annotations
 
@@ -31,7 +38,18 @@ from ._lib import CfdAabb, CfdError, CfdPoint, check, load
 
 __all__ = ["Point", "AABB", "Polygon", "PolygonError", "PolygonException", "do_intersect",
            "line_segment_intersection", "intersect_quad_edge", "tesselate", "QuadTree", "Mesh",
-           "Cell", "default_polygon"]
+           "Cell", "default_polygon", "rasterize_polygon", "rasterize_quad_tree",
+           "rasterize_mesh", "rasterize_mesh_no_background", "mesh_view_image", "mesh_view_size",
+           "TRANSPARENT", "BLACK", "LIGHT_BLUE", "ORANGE"]
+
+# egui::Color32 constants as (r, g, b, a) bytes (include/cfd.h)
+TRANSPARENT = (0, 0, 0, 0)
+BLACK = (0, 0, 0, 255)
+LIGHT_BLUE = (173, 216, 230, 255)
+ORANGE = (255, 165, 0, 255)
+
+# device ms of the last rasteriser call's kernels (HIP events)
+last_raster_ms: Optional[float] = None
 
 
 @dataclass(frozen=True)
@@ -301,9 +319,19 @@ class Mesh:
             ms = C.c_double()
             check("cfd_mesh_build_ms", L.cfd_mesh_build_ms(h, C.byref(ms)))
             m.build_ms = float(ms.value)
-        finally:
+        except BaseException:
             L.cfd_mesh_destroy(h)
+            raise
+        m._h = h   # kept for the rasterisers
         return m
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                load().cfd_mesh_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
 
     @property
     def num_cells(self) -> int:
@@ -330,3 +358,82 @@ class Mesh:
 
     def full_bounding_box(self) -> AABB:
         return self._bbox
+
+
+# ------------------------------------------------------------ Mesh tab images
+
+_U8P = C.POINTER(C.c_uint8)
+
+
+def _raster(name: str, w: int, h: int, call) -> np.ndarray:
+    """Run one cfd_raster_* call into a fresh (h, w, 4) image."""
+    global last_raster_ms
+    if w is None or h is None or w < 0 or h < 0:
+        raise CfdError(name, -1, "image size missing or negative")
+    # sizes outside [2, 16384] are refused by the library before it writes
+    ok = 2 <= w <= 16384 and 2 <= h <= 16384
+    img = np.empty((h, w, 4) if ok else (1, 1, 4), np.uint8)
+    ms = C.c_double()
+    check(name, call(img.ctypes.data_as(_U8P), C.byref(ms)))
+    last_raster_ms = float(ms.value)
+    return img
+
+
+def _background(background) -> np.ndarray:
+    bg = np.ascontiguousarray(background, dtype=np.uint8)
+    if bg.ndim != 3 or bg.shape[2] != 4:
+        raise ValueError("background must be an (h, w, 4) uint8 image")
+    return bg
+
+
+def rasterize_polygon(polygon: Polygon, w: int, h: int, device: int = 0) -> np.ndarray:
+    """PolygonRasterizer::rasterize (polygon_rasterizer.rs:22-103)."""
+    return _raster("cfd_raster_polygon", w, h, lambda out, ms: load().cfd_raster_polygon(
+        polygon._h, device, w, h, out, ms))
+
+
+def rasterize_quad_tree(tree: QuadTree, w: Optional[int] = None, h: Optional[int] = None,
+                        background=None, bbox: Optional[AABB] = None,
+                        device: int = 0) -> np.ndarray:
+    """rasterize_quad_tree (background and bbox given, quad_tree_rasterizer.rs:15-22)
+    or rasterize_quad_tree_no_background (:6-13: transparent, the tree's boundary)."""
+    bg = None if background is None else _background(background)
+    if bg is not None:
+        h, w = bg.shape[:2]
+    box = None if bbox is None else bbox._c()
+    return _raster("cfd_raster_quadtree", w, h, lambda out, ms: load().cfd_raster_quadtree(
+        tree._h, None if box is None else C.byref(box), device, w, h,
+        None if bg is None else bg.ctypes.data_as(_U8P), out, ms))
+
+
+def rasterize_mesh(mesh: "Mesh", background, bbox: AABB, device: int = 0) -> np.ndarray:
+    """rasterize_mesh (mesh_rasterizer.rs:16-22); the background is not modified."""
+    bg, box = _background(background), bbox._c()
+    h, w = bg.shape[:2]
+    return _raster("cfd_raster_mesh", w, h, lambda out, ms: load().cfd_raster_mesh(
+        mesh._h, C.byref(box), device, w, h, bg.ctypes.data_as(_U8P), out, ms))
+
+
+def rasterize_mesh_no_background(mesh: "Mesh", w: int, h: int, bbox: AABB,
+                                 device: int = 0) -> np.ndarray:
+    """rasterize_mesh_no_background (mesh_rasterizer.rs:8-12)."""
+    box = bbox._c()
+    return _raster("cfd_raster_mesh", w, h, lambda out, ms: load().cfd_raster_mesh(
+        mesh._h, C.byref(box), device, w, h, None, out, ms))
+
+
+def mesh_view_image(polygon: Polygon, mesh: Optional["Mesh"], w: int, h: int,
+                    device: int = 0) -> np.ndarray:
+    """The sketch image of MeshView::draw_sketch (views/mesh_view.rs:86-94): the
+    polygon raster with the mesh, if any, over it, in one device pass."""
+    return _raster("cfd_raster_mesh_view", w, h, lambda out, ms: load().cfd_raster_mesh_view(
+        polygon._h, None if mesh is None else mesh._h, device, w, h, out, ms))
+
+
+def mesh_view_size(bbox: AABB, avail_w: float, avail_h: float) -> Tuple[int, int]:
+    """(width, height) of the image draw_sketch makes for an available panel
+    of avail_w x avail_h (views/mesh_view.rs:75-88).  Host only."""
+    box, w, h = bbox._c(), C.c_size_t(), C.c_size_t()
+    check("cfd_mesh_view_size", load().cfd_mesh_view_size(C.byref(box), avail_w, avail_h,
+                                                          C.byref(w), C.byref(h)))
+    return int(w.value), int(h.value)

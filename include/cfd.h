@@ -732,6 +732,54 @@ int cfd_mesh_full_bounding_box(const cfd_mesh *m, cfd_aabb *out);               
 int cfd_mesh_build_ms(const cfd_mesh *m, double *ms);
 void cfd_mesh_destroy(cfd_mesh *m);
 
+/* ---- the Mesh tab's images (src/utils/polygon_rasterizer.rs,
+ * quad_tree_rasterizer.rs, mesh_rasterizer.rs, drawing.rs) ----
+ * Drawn on HIP device `device`; only the w*h*4 bytes of the image leave it.
+ * Part of the ABI:
+ *   - RGBA8, 4 bytes per pixel, row-major, x fastest; row 0 is the reference's
+ *     y = 0 (the reference does not flip, neither does this).
+ *   - The colours are egui's Color32 constants as bytes:
+ *       TRANSPARENT (0, 0, 0, 0)        BLACK  (0, 0, 0, 255)
+ *       LIGHT_BLUE  (173, 216, 230, 255)   from_rgb(0xAD, 0xD8, 0xE6)
+ *       ORANGE      (255, 165, 0, 255)     from_rgb(255, 165, 0)
+ *   - The arithmetic is the reference's f64: scale = min((w - 1) / bbox.width(),
+ *     (h - 1) / bbox.height()), pixel = floor((x - top_left.x) * scale) cast as
+ *     each rasteriser casts it (`as usize` then `as isize` for the polygon and
+ *     the quadtree: negatives and NaN give 0; straight `as isize` for the mesh:
+ *     negatives stay and are clipped per pixel), draw_line and draw_diamond
+ *     pixel for pixel, and the reference's drawing order (fill, polygon edges,
+ *     cells in ascending index, each cell's outline before its diamonds).
+ * Build-defined limits, checked on the host before any launch (the reference
+ * has none: it would walk a far-off line for as long as it takes): w and h in
+ * [2, 16384]; a finite bbox of positive width and height; every segment end
+ * and diamond centre within [-32768, 32768] pixels; polygon holes without
+ * holes of their own (as cfd_mesh_from_quadtree).  CFD_EINVAL for these and
+ * for NULL handles or outputs, with nothing written.  device_ms may be NULL;
+ * otherwise it receives the device time of the call's kernels (HIP events).
+ * `background` and `rgba` are w*h*4 bytes and may be the same buffer. */
+/* PolygonRasterizer::rasterize (polygon_rasterizer.rs:44-103) on the polygon's
+ * own bounding box. */
+int cfd_raster_polygon(const cfd_polygon *p, int device, size_t w, size_t h, uint8_t *rgba,
+                       double *device_ms);
+/* rasterize_quad_tree / rasterize_quad_tree_no_background
+ * (quad_tree_rasterizer.rs:6-59).  NULL bbox: the tree's boundary; NULL
+ * background: transparent. */
+int cfd_raster_quadtree(const cfd_quadtree *t, const cfd_aabb *bbox, int device, size_t w, size_t h,
+                        const uint8_t *background, uint8_t *rgba, double *device_ms);
+/* rasterize_mesh / rasterize_mesh_no_background (mesh_rasterizer.rs:8-57).
+ * bbox is required; NULL background: transparent.  A mesh of 0 cells gives
+ * the background. */
+int cfd_raster_mesh(const cfd_mesh *m, const cfd_aabb *bbox, int device, size_t w, size_t h,
+                    const uint8_t *background, uint8_t *rgba, double *device_ms);
+/* The first image of MeshView::draw_sketch (views/mesh_view.rs:86-94): the
+ * polygon raster with the mesh (if any) over it, on the polygon's bounding
+ * box, in one device pass. */
+int cfd_raster_mesh_view(const cfd_polygon *p, const cfd_mesh *mesh_or_null, int device, size_t w,
+                         size_t h, uint8_t *rgba, double *device_ms);
+/* The image-size rule of views/mesh_view.rs:75-88: the available aspect is an
+ * f32 division widened to f64, the sizes are truncated `as usize`.  Host only. */
+int cfd_mesh_view_size(const cfd_aabb *bbox, float avail_w, float avail_h, size_t *w, size_t *h);
+
 const char *cfd_last_error(void);
 int cfd_abi_version(void);
 void cfd_destroy(cfd_model *m);
